@@ -11,10 +11,18 @@ tables, start states, seeded MT19937 states) are resident in HBM before the time
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  value = expansions of ALL ranks / max-over-ranks time.  The other configurations of
-BASELINE.json ride along as side measurements in the same line (each with its own step time, kernel time, roofline
-and -- at N = 1 -- CPU baseline); for N > 1 the A* batch (config 3) and the Planner_RRT batch (config 4) are sharded
-over the ranks like the headline and gathered the same way.
+Rank 0 prints ONE JSON line.  value = expansions of ALL ranks / max-over-ranks time.  A plain run sets up, warms up, times
+the K steps and prints that line (the headline's roofline is derived from the timed steps' own kernel times and the
+committed counter passes: no launch of its own).  With --full the other configurations of BASELINE.json ride along as
+side measurements in the same line (each with its own step time, kernel time, roofline and -- at N = 1 -- CPU
+baseline), with the measured HBM roof and the headline's CPU baselines; for N > 1 the A* batch (config 3) and the
+Planner_RRT batch (config 4) are sharded over the ranks like the headline and gathered the same way.  --only implies
+--full.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's episodes) as float64 .npy files:
+every field of the result records, summary_<field>.npy, and the best paths of a fixed, seeded sample of the episodes,
+best_paths.npy with best_path_offsets.npy and best_path_episodes.npy.  The inputs are seeded: two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -301,9 +309,43 @@ def spawn_ranks(n):
     sys.exit(rc)
 
 
+DUMP_LIMIT = 64 << 20  # bytes, all files of --dump-outputs together
+DUMP_PATH_EPISODES = 512  # the fixed, seeded sample of episodes whose best paths are written
+
+
+def dump_outputs(d, summ, off, paths_dev):
+    """--dump-outputs: the result records of the last timed step (summary_<field>.npy, one row per episode) and the best paths
+    (root -> leaf, [L,7]) of DUMP_PATH_EPISODES episodes drawn with a fixed seed, concatenated (best_paths.npy; the rows of
+    best_path_episodes[i] are best_path_offsets[i]:best_path_offsets[i + 1]); episodes are dropped from the end of the sample
+    should their paths not fit DUMP_LIMIT"""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    used = 0
+    for name in summ.dtype.names:
+        a = summ[name].astype(np.float64)  # (every integer field is far below 2**53: exact)
+        np.save(os.path.join(d, "summary_%s.npy" % name), a)
+        used += a.nbytes
+    E = len(summ)
+    eps = np.sort(np.random.default_rng(0).choice(E, size=min(E, DUMP_PATH_EPISODES), replace=False))
+    lens = off[eps + 1] - off[eps]
+    keep = int(np.searchsorted(np.cumsum(lens) * 7 * 8, DUMP_LIMIT - used - 2 * 8 * (len(eps) + 1) - 4096, side="right"))
+    eps, lens = eps[:keep], lens[:keep]
+    rows = np.concatenate([np.arange(off[e], off[e + 1]) for e in eps] + [np.zeros(0, dtype=np.int64)])
+    pts = paths_dev[torch.from_numpy(rows).to(paths_dev.device)].cpu().numpy() if len(rows) else np.zeros((0, 7))
+    p_off = np.zeros(len(eps) + 1)
+    np.cumsum(lens, out=p_off[1:])
+    np.save(os.path.join(d, "best_paths.npy"), pts.astype(np.float64))
+    np.save(os.path.join(d, "best_path_offsets.npy"), p_off)
+    np.save(os.path.join(d, "best_path_episodes.npy"), eps.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the measured HBM roof, the CPU baselines and every "
+                                                        "side measurement (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result records and a seeded sample of its best paths to DIR/*.npy")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements")
     ap.add_argument("--only", default="", help="comma list of side measurements to run INSTEAD of the headline "
                                                 "(astar, planner_rrt, config5, rrt_dense, ...): profiling passes")
     ap.add_argument("--gpus", type=int, default=1)
@@ -317,7 +359,7 @@ def main():
     ap.add_argument("--grid", type=int, default=200, help="grid is grid x grid cells of 10 m")
     ap.add_argument("--mode", default="timebin", choices=["timebin", "nn", "plantime"])
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-variants", action="store_true", help="config 3 only, without the other A* variants (counter passes)")
     args = ap.parse_args()
 
@@ -328,10 +370,11 @@ def main():
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     args.gpus = world_size
     only = [s for s in args.only.split(",") if s]
+    args.full = args.full or bool(only)
     args.episodes_fit = args.episodes
 
     world = bench_world(args.obstacles, args.grid)
-    with_cpu = world_size == 1 and not args.no_cpu
+    with_cpu = args.full and world_size == 1 and not args.no_cpu
     cpu_all = None
     if with_cpu and not only:
         cpu_all = cpu_baseline_all_cores(world, args.iters, args)  # forks: must precede any HIP initialisation
@@ -357,7 +400,7 @@ def main():
     ctx = _lib.Context(local_rank)
     # (one GPU + a stand-in RCCL named by AUVP_RCCL_LIBRARY: the C-ABI transport runs too -- tests/test_gpu_bench_two_ranks.py)
     ranks = Ranks(ctx, rank, world_size, dev, use_rccl=(not one_gpu) or bool(os.environ.get("AUVP_RCCL_LIBRARY")), cpu_group=one_gpu)
-    if rank == 0:
+    if rank == 0 and args.full:
         measure_hbm(ctx)  # 4 GiB streaming read + copy, a few ms: the measured roof every roofline object quotes
     sides = {
         "single_episode": lambda: bench_single_episode(ctx, world, args),
@@ -410,6 +453,7 @@ def main():
     seeds = np.arange(rank * E, (rank + 1) * E, dtype=np.uint64)  # global episode id = seed
     ctx.rrt_prepare(init, seeds, args.iters, mode=args.mode, **RRT_KW)
     kms, gms, parts = [], [], []
+    last = {}  # the last step's path offsets and device paths (--dump-outputs)
 
     def step():
         """expansion + leaf pass + best-path extraction (+ RCCL gather of the result records for N > 1).  From the second step on the
@@ -424,8 +468,10 @@ def main():
         off = np.zeros(E + 1, dtype=np.int64)
         np.cumsum(lens, out=off[1:])
         total = int(off[-1])
+        last.clear()  # (the step before's paths go back to the allocator before this step's are allocated)
         paths = torch.empty((max(total, 1), 7), dtype=torch.float64, device=dev)
         ctx.paths_dev(off, paths.data_ptr())  # best paths stay in HBM
+        last.update(off=off, paths=paths)
         if world_size > 1 and gather_mode == "all":
             # (AUVP_BENCH_GATHER=all) every rank receives every record: the fixed-stride result records straight from the
             # planner's device buffer + the variable-length paths, waited for inside the step
@@ -464,6 +510,9 @@ def main():
     bad = summ["status"] < 0
     if bad.any():
         sys.exit("device error status in %d episodes: %s" % (int(bad.sum()), np.unique(summ["status"][bad])))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, summ, last["off"], last["paths"])
+    last.clear()
     iters_local = float(summ["iters_run"].sum())
     iters_per_step = ranks.sum(iters_local)
     acc_per_step = ranks.sum(float((summ["n_nodes"] - 1).sum()))
@@ -524,14 +573,15 @@ def main():
             "qualifying_leaves_per_episode": float(summ["n_leaves"].mean()),
             "cull_candidates_per_expansion": float(summ["n_candidates"].sum()) / iters_local,
         }
-        out["hbm_probe"] = dict(HBM_MEASURED, peak_spec_GBps=HBM_PEAK_GBS,
-                                note="auvp_hbm_probe: best of `reps` launches; read = 8 x 16 B loads in flight per lane, copy = bytes read + written")
+        if args.full:
+            out["hbm_probe"] = dict(HBM_MEASURED, peak_spec_GBps=HBM_PEAK_GBS,
+                                    note="auvp_hbm_probe: best of `reps` launches; read = 8 x 16 B loads in flight per lane, copy = bytes read + written")
         if with_cpu:
             out["cpu_baseline"] = cpu_baseline(world, args.iters, args)
             out["cpu_baseline_all_cores"] = cpu_all
         else:
             out["cpu_baseline"] = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # the other configurations of the path: configs 3, 4 and 5 on every rank (sharded), the rest on rank 0's GPU
         for name in ("single_episode", "rrt_64_obstacles", "rrt_1024_replicas", "rrt_dense", "rrt_nn", "rrt_nn_long_horizon", "astar", "planner_rrt", "rrt_env", "config5", "shark_grid",
                      "particle_filter"):

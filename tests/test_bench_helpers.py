@@ -185,3 +185,43 @@ def test_compact_string_never_exceeds_the_limit_and_never_raises():
     line = json.loads(s)
     assert len(s) <= b.LINE_LIMIT and line["value"] == 2.5 and line["roofline"]["frac"] == 0.116
     assert line["config"]["gather_bytes_per_rank"] == 1.2e8 and line["config"]["gather_ms_over_step"] == 0.03
+
+
+def test_dump_outputs_writes_float_arrays_of_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: every record field as float64, the best paths of the same seeded sample of episodes on every call,
+    at most 64 MB in all (episodes are dropped from the end of the sample when their paths do not fit).  A host tensor stands
+    in for the device buffer the paths are read from."""
+    import torch
+    b = _bench()
+    from auv_sim_amd import _lib
+    E = 2000
+    s = np.zeros(E, dtype=_lib.SUMMARY_DTYPE)
+    s["n_nodes"] = np.arange(E) + 1
+    s["best_cost"] = np.arange(4 * E, dtype=np.float64).reshape(E, 4) * 0.5
+    lens = np.arange(E, dtype=np.int64) % 7
+    off = np.zeros(E + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    paths = torch.arange(int(off[-1]) * 7, dtype=torch.float64).reshape(-1, 7)
+    b.dump_outputs(str(tmp_path / "a"), s, off, paths)
+    b.dump_outputs(str(tmp_path / "b"), s, off, paths)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"summary_%s.npy" % n for n in _lib.SUMMARY_DTYPE.names} | {"best_paths.npy", "best_path_offsets.npy", "best_path_episodes.npy"} == set(names)
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(np.load(tmp_path / "a" / "summary_n_nodes.npy"), s["n_nodes"].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "summary_best_cost.npy"), s["best_cost"])
+    eps = np.load(tmp_path / "a" / "best_path_episodes.npy").astype(np.int64)
+    p_off = np.load(tmp_path / "a" / "best_path_offsets.npy").astype(np.int64)
+    pts = np.load(tmp_path / "a" / "best_paths.npy")
+    assert len(eps) == b.DUMP_PATH_EPISODES and len(set(eps.tolist())) == len(eps) and len(p_off) == len(eps) + 1
+    for i, e in enumerate(eps):
+        assert np.array_equal(pts[p_off[i]:p_off[i + 1]], paths[off[e]:off[e + 1]].numpy())
+    # long paths: the sample is cut to the limit
+    big = np.arange(E + 1, dtype=np.int64) * 20000
+    b.dump_outputs(str(tmp_path / "c"), s, big, torch.zeros((int(big[-1]), 7), dtype=torch.float64))
+    total = sum(os.path.getsize(tmp_path / "c" / n) for n in os.listdir(tmp_path / "c"))
+    kept = np.load(tmp_path / "c" / "best_path_episodes.npy")
+    assert total <= b.DUMP_LIMIT == 64 << 20 and 0 < len(kept) < b.DUMP_PATH_EPISODES
+    assert np.load(tmp_path / "c" / "best_paths.npy").shape == (20000 * len(kept), 7)

@@ -26,7 +26,7 @@ def _bench(gpus, episodes, extra=(), one_gpu=False, more_env=None):
     if one_gpu:
         env["AUVP_BENCH_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "0",
-           "--episodes", str(episodes), "--iters", "300", "--no-cpu"] + list(extra)
+           "--episodes", str(episodes), "--iters", "300", "--no-cpu", "--full"] + list(extra)
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

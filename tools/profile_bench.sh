@@ -1,9 +1,9 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): rocprofv3 kernel-trace stats + PMC passes of bench.py.
 # usage: tools/profile_bench.sh <tag> [--sides "a b c"] [--no-headline] [bench args...]; writes gpurun_out/prof_<tag>/
-#   bench.json     the plain default command (what the driver runs): its compact final line; bench_sides.json = the full record
+#   bench.json     bench.py --full (the headline with every side measurement): its compact final line; bench_sides.json = the full record
 #   trace_main     headline kernel alone (--no-extra): its average must agree with roofline.kernel_ms
-#   trace          the full default command (every side measurement)
+#   trace          bench.py --full (every side measurement)
 #   pmc@headline@<C>   counters of the headline launch, one pass per counter group (counters only: no trace flags); one warm-up
 #                      step + one step: the first batch with a parameter block runs rrt_rows_kernel, the measured ones the stream kernels
 #   trace_<side>, pmc@<side>@<C>   the same for one side measurement (bench.py --only <side>); default sides below
@@ -32,11 +32,11 @@ G_LANES="SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_I
 if [ $HEADLINE = 1 ]; then
   # bench.py prints the compact (<= 4 KB) line; the full record with every side measurement goes to $AUVP_BENCH_SIDES
   export AUVP_BENCH_SIDES=$OUT/bench_sides.json
-  AUVP_BENCH_PROFILE=0 python3 $R/bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
+  AUVP_BENCH_PROFILE=0 python3 $R/bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench.err
   export AUVP_BENCH_SIDES=$OUT/trace_main_bench.sides.json
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_main -o trace_main -- python3 $R/bench.py $ARGS --no-cpu --no-extra > $OUT/trace_main_bench.json 2> $OUT/trace_main.err
   export AUVP_BENCH_SIDES=$OUT/trace_bench.sides.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/bench.py $ARGS --no-cpu > $OUT/trace_bench.json 2> $OUT/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/bench.py --full $ARGS --no-cpu > $OUT/trace_bench.json 2> $OUT/trace.err
   for P in "$G_FETCH" "$G_WRITE" "$G_INSTS" "$G_ACTIVE" "$G_LANES"; do
     N=$(echo $P | cut -d" " -f1)
     export AUVP_BENCH_SIDES=$OUT/pmc@headline@$N.sides.json
