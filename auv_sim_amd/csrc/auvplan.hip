@@ -59,12 +59,12 @@ struct DevBuf {
 enum AuvpOpt {
   OPT_ROWS, OPT_DUO, OPT_TRIO, OPT_QUAD, OPT_TIGHT_CULL, OPT_NN_EXACT, OPT_LEAF_SWEEP_ALL, OPT_NO_HABITAT_GRID, OPT_RG_MAX_ENTRIES,
   OPT_NO_GRID_INDEX, OPT_PRRT_LAT, OPT_PRRT_PIPE, OPT_PRRT_OBST_LDS, OPT_PRRT_NEXT_LDS, OPT_PRRT_ROWS, OPT_ASTAR_NO_GRID,
-  OPT_ASTAR_NO_LIST, OPT_ASTAR_PAIR, OPT_SOG_TILE, OPT_PIPE_FALLBACK, OPT_PRRT_PIPE_DRAW, OPT_PRRT_BUCKET_LDS, OPT_ROWS_STREAM, OPT_ROWS_STREAM_CAP, OPT_ROWS_STREAM_WAVES, OPT_COUNT
+  OPT_ASTAR_NO_LIST, OPT_ASTAR_PAIR, OPT_SOG_TILE, OPT_PIPE_FALLBACK, OPT_PRRT_PIPE_DRAW, OPT_PRRT_BUCKET_LDS, OPT_ROWS_STREAM, OPT_ROWS_STREAM_CAP, OPT_ROWS_STREAM_WAVES, OPT_ROWS_WG_WAVES, OPT_COUNT
 };
 static const char* const AUVP_OPT_NAMES[OPT_COUNT] = {
   "ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
   "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
-  "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES"};
+  "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES", "ROWS_WG_WAVES"};
 
 struct auvp_handle {
   bool opt_has[OPT_COUNT] = {};
@@ -945,7 +945,9 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
     if (n_cu <= 0) n_cu = 256;
-    int wg_waves = (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu);
+    // (option ROWS_WG_WAVES: the waves per workgroup instead, both forms of the kernel -- tests: small batches at the shapes
+    // only full-chip batches get otherwise)
+    int wg_waves = (int)h->opt_num(OPT_ROWS_WG_WAVES, (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu));
     wg_waves = wg_waves < 1 ? 1 : (wg_waves > RW_WAVES ? RW_WAVES : wg_waves);
     const RowsLdsPlan rq = rrt_rows_lds_plan(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), wg_waves);
     const int per_wg = wg_waves * RW_ROWS;
@@ -987,7 +989,7 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
       // without the generator's state an episode needs 2.3 KB of LDS instead of 3.3: a CU holds 64 of them -- sixteen wavefronts,
       // four per SIMD -- but that instantiation spills (rows_kernels.hip): twelve at most, like rrt_rows_kernel (option
       // ROWS_STREAM_WAVES: fewer, for experiments)
-      int sw = (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu);
+      int sw = (int)h->opt_num(OPT_ROWS_WG_WAVES, (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu));
       const int sw_max = (int)h->opt_num(OPT_ROWS_STREAM_WAVES, RW_WAVES);  // (the four-per-SIMD form measured 0.93 G expansions/s against 1.16: 100 B of scratch per lane at 128 registers)
       sw = sw < 1 ? 1 : (sw > sw_max ? sw_max : sw);
       sw = sw > RW_WAVES ? RW_WAVES : sw;

@@ -3,7 +3,8 @@
 Every case draws a world and planner parameters at random and compares, bit for bit, the four-episode-per-wavefront
 kernel, the one-episode kernel and the CPU checker (RRT.exploring, time-bin sampling; nearest-neighbour -- scan and fallback --
 and plan-time sampling), the astar_fixLenSOG / astar_fixLen searches and Planner_RRT.planning (latency, throughput and
-four-episodes-per-wavefront kernels) with the checker.  Prints one line per failure and a summary; exit code 1 on any mismatch."""
+four-episodes-per-wavefront kernels) with the checker.  The four-episode kernel runs at a drawn workgroup size (option
+ROWS_WG_WAVES: unset, 1, 2, 5, 7 or 12 waves).  Prints one line per failure and a summary; exit code 1 on any mismatch."""
 import os
 import random
 import sys
@@ -42,18 +43,25 @@ def rrt_case(i):
               min_dist=rng.choice([0.0, 0.5, 1.5]), bin_interval=rng.choice([2.5, 5.0, 20.0]), v=rng.choice([0.7, 2.0]),
               max_traj_time=rng.choice([40.0, 120.0, 500.0]),
               weights=(rng.choice([-3.0, 0.0, 2.5]), rng.choice([-3.0, -0.37, 4.0]), rng.choice([-4.0, 0.0, 1.7])))
-    E, n_iter = (rng.choice([1, 5, 9]), rng.choice([200, 700, 1500])) if not BIG else (2, rng.choice([4000, 8000]))
+    E, n_iter = (rng.choice([1, 5, 9, 13, 30]), rng.choice([200, 700, 1500])) if not BIG else (2, rng.choice([4000, 8000]))
+    # the four-episode kernel's waves per workgroup (option ROWS_WG_WAVES; None: the host's, one wave at these sizes): batches
+    # of 13 and 30 leave the last workgroup partial at 2, 5, 7 and 12 waves
+    wg = rng.choice([None, 1, 2, 5, 7, 12])
     ctx.set_world(w["obstacles"], w["habitats"], w["polygon"], w["bins"], w["cells"], w["prob"])
     init = np.zeros((E, 6)); init[:, 0], init[:, 1] = w["start"]; init[:, 2] = np.linspace(-3, 3, E)
     seeds = np.array([rng.randrange(2 ** 40) for _ in range(E)], dtype=np.uint64)
     res = {}
     for rows in ("1", "0"):
         os.environ["AUVP_ROWS"] = rows
+        if rows == "1" and wg is not None:
+            os.environ["AUVP_ROWS_WG_WAVES"] = str(wg)
+        else:
+            os.environ.pop("AUVP_ROWS_WG_WAVES", None)
         for tight in ("0", "1"):
             os.environ["AUVP_TIGHT_CULL"] = tight
             s = ctx.rrt_explore_batch(init, seeds, n_iter, **kw).copy()
             res[rows + tight] = (s, [ctx.tree(e, s[e]) for e in range(E)], ctx.paths(s))
-    os.environ.pop("AUVP_ROWS"); os.environ.pop("AUVP_TIGHT_CULL")
+    os.environ.pop("AUVP_ROWS"); os.environ.pop("AUVP_TIGHT_CULL"); os.environ.pop("AUVP_ROWS_WG_WAVES", None)
     wo = orc.WorldArrays(w["obstacles"], w["habitats"], w["polygon"], w["bins"], w["cells"], w["prob"])
     for e in range(E):
         r = orc.rrt_explore(wo, int(seeds[e]), n_iter, init=init[e], kind="portable", **kw)
@@ -66,7 +74,7 @@ def rrt_case(i):
                 ok = np.array_equal(np.array(s[e]["best_cost"]), r["best_cost"]) and np.array_equal(p[e], r["path"])
             if not ok:
                 fails += 1
-                print("RRT MISMATCH case", i, "episode", e, "variant rows/tight", key, kw, "obst", nob)
+                print("RRT MISMATCH case", i, "episode", e, "variant rows/tight", key, kw, "obst", nob, "waves per workgroup", wg)
 
 
 def rrt_modes_case(i):
