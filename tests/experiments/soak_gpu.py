@@ -116,8 +116,14 @@ def rrt_modes_case(i):
 def astar_case(i):
     global fails
     cell = rng.choice([5.0, 10.0, 14.0, 20.0])
-    w = synth.make_world(seed=rng.randrange(10 ** 6), n_obstacles=rng.choice([0, 20, 64]), obst_radius=(2.0, rng.choice([4.0, 8.0])),
-                         n_habitats=rng.choice([0, 5, 12]), hab_radius=(8.0, 25.0), cell=cell)
+    # obstacle lists up to, at and past the 256 the kernel stages in LDS (smaller radii for the long ones); habitat and time-bin
+    # tables up to their cap of 64
+    nob = rng.choice([0, 20, 64, 256, 257, 600])
+    n_bins = rng.choice([1, 10, 10, 33, 64])
+    w = synth.make_world(seed=rng.randrange(10 ** 6), n_obstacles=nob,
+                         obst_radius=(2.0, rng.choice([4.0, 8.0])) if nob <= 64 else (0.5, rng.choice([1.5, 2.5])),
+                         n_habitats=rng.choice([0, 5, 12, 33, 64]), hab_radius=(8.0, 25.0), cell=cell, n_bins=n_bins,
+                         bin_len=500 // n_bins + 1)
     off = rng.choice([0.0, 0.0, 0.37])
     starts = np.array([(-290.0 + 10.0 * rng.randrange(0, 10) + off, -90.0 + 10.0 * rng.randrange(0, 10) + off) for _ in range(6)])
     variant = rng.choice(["astar_fixLenSOG", "astar_fixLenSOG", "astar_fixLen"])

@@ -797,6 +797,64 @@ def g6():
         print("g6 sog", k, "found", out["found"], "path", out.get("path_length"), "expansions", len(out["expansions"]))
 
 
+def g6o():
+    """The four A* variants at and past the 256 obstacles the kernel stages in LDS (astar_kernel.h ASTAR_LDS_OBST; beyond it
+    the collision tests read the obstacle arrays from memory).  Each world is built so that its LAST obstacle decides the
+    result: the search runs without it, then it is placed (r = 1.5 m: one lattice point) on the middle node of the path found.
+    Writes g1_* / g6_* fixtures, so the globs of the A* golden tests pick them up."""
+    rect = [(-300.0, -100.0), (-100.0, -100.0), (-100.0, 100.0), (-300.0, 100.0)]
+    last_r = 1.5
+
+    def place_last(obstacles, path):
+        p = path[len(path) // 2]
+        return np.vstack([np.asarray(obstacles, dtype=np.float64).reshape(-1, 3), [[float(p[0]), float(p[1]), last_r]]])
+
+    # astar_fixLenSOG: name, seed, obstacle count, start, limit, weights, polygon
+    sog = [("g6_sog_o256", 41, 256, (-290.0, -90.0), 200, (0, 10, 10, 100), None),
+           ("g6_sog_o257_catalina", 42, 257, (-180.0, -20.0), 150, (0, 10, 10, 100), "catalina"),
+           ("g6_sog_o600", 43, 600, (-250.0, -60.0), 200, (0, 10, 10, 100), None)]
+    for name, seed, nobs, st, limit, wts, polygon in sog:
+        w = synth.make_world(seed=seed, n_obstacles=nobs - 1, obst_radius=(0.5, 2.5), start=st, n_habitats=8,
+                             hab_radius=(10.0, 25.0), polygon=polygon)
+        first = run_astar_sog(w, st, limit, wts)
+        assert first["found"], name
+        w["obstacles"] = place_last(w["obstacles"], first["node_path"])
+        out = run_astar_sog(w, st, limit, wts)
+        save_npz(name + ".npz", **out)
+        print(name, "found", out["found"], "path", out.get("path_length"), "expansions", len(out["expansions"]),
+              "without the last obstacle", len(first["expansions"]))
+    # astar_fixLen
+    for name, seed, nobs, st, limit, wts in (("g6_fixlen_o256", 44, 256, (-290.0, -90.0), 200, (0, 10, 10)),
+                                             ("g6_fixlen_o600", 45, 600, (-200.0, 0.0), 300, (0, 10, 10))):
+        w = synth.make_world(seed=seed, n_obstacles=nobs - 1, obst_radius=(0.5, 2.5), start=st, n_habitats=8,
+                             hab_radius=(10.0, 25.0))
+        first = run_astar_fixlen(w["obstacles"].tolist(), w["habitats"].tolist(), rect, st, limit, wts)
+        assert first["found"], name
+        obs = place_last(w["obstacles"], first["path"])
+        out = run_astar_fixlen(obs.tolist(), w["habitats"].tolist(), rect, st, limit, wts)
+        save_npz(name + ".npz", **out)
+        print(name, "found", out["found"], "path", len(out.get("path", [])), "expansions", len(out["expansions"]),
+              "without the last obstacle", len(first["expansions"]))
+    # astar_real
+    st, gl = (-290.0, -90.0), (-110.0, 90.0)
+    w = synth.make_world(seed=46, n_obstacles=299, obst_radius=(0.5, 2.5), start=st)
+    obs = [o for o in w["obstacles"].tolist() if (o[0] - gl[0]) ** 2 + (o[1] - gl[1]) ** 2 > (o[2] + 12) ** 2]
+    first = run_astar_real(obs, rect, st, gl)
+    assert first["found"]
+    out = run_astar_real(place_last(obs, first["path"]).tolist(), rect, st, gl)
+    save_npz("g1_real_o300.npz", **out)
+    print("g1_real_o300 obstacles", len(out["obstacles"]), "found", out["found"], "path", len(out["path"]),
+          "expansions", len(out["expansions"]))
+    # astar (lattice world)
+    w = synth.make_lattice_world(seed=47, n_obstacles=299, r_range=(3, 8))
+    first = run_astar_basic(w, (0, 0), (490, 490))
+    assert first["found"]
+    w["obstacles"] = place_last(w["obstacles"], first["path"])
+    out = run_astar_basic(w, (0, 0), (490, 490))
+    save_npz("g1_astar_o300.npz", **out)
+    print("g1_astar_o300 found", out["found"], "path", len(out["path"]), "expansions", len(out["expansions"]))
+
+
 def g6b():
     """two astar() calls on ONE astar_fixLen solver: self.visited_nodes carries over (:51,:414-416)"""
     mod, mpsm = import_astar("astar_fixLen")
@@ -1378,8 +1436,8 @@ def g15():
     np.savez_compressed(os.path.join(OUT, "g15_shark_grid_csv.npz"), **out)
 
 
-ALL = {"g15": g15, "g7": g7, "g5": g5, "g4": g4, "g3": g3, "g2": g2, "g1": g1, "g6": g6, "g6b": g6b, "g8": g8, "g9": g9,
-       "g10": g10, "g11": g11, "g12": g12, "g13": g13, "g14": g14}
+ALL = {"g15": g15, "g7": g7, "g5": g5, "g4": g4, "g3": g3, "g2": g2, "g1": g1, "g6": g6, "g6o": g6o, "g6b": g6b, "g8": g8,
+       "g9": g9, "g10": g10, "g11": g11, "g12": g12, "g13": g13, "g14": g14}
 
 # the fast subset `--check` regenerates by default (seconds of reference Python each); AUVP_G3_ONLY narrows g3
 FAST = ("g7", "g5", "g4", "g1", "g12", "g14", "g15")

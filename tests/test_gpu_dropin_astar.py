@@ -36,7 +36,8 @@ def test_astar_real():
     assert [(p.x, p.y) for p in path] == [tuple(r) for r in g["path"].tolist()]
 
 
-@pytest.mark.parametrize("name", ["g6_fixlen_1", "g6_fixlen_4"])  # a pentagon; (round 6) a CONCAVE outline: the centroid fan's quirk
+@pytest.mark.parametrize("name", ["g6_fixlen_1", "g6_fixlen_4",  # a pentagon; (round 6) a CONCAVE outline: the centroid fan's quirk
+                                  "g6_fixlen_o256", "g6_fixlen_o600"])  # a full LDS obstacle table, and obstacles read from memory
 def test_astar_fixlen_mutates_habitat_list_like_reference(name):
     from auv_sim_amd.astar_fixLen import astar
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
@@ -48,7 +49,8 @@ def test_astar_fixlen_mutates_habitat_list_like_reference(name):
     assert [[h.x, h.y, h.size] for h in hab] == g["habitats_left"].tolist()
 
 
-@pytest.mark.parametrize("name", ["g6_sog_0", "g6_sog_1", "g6_sog_2", "g6_sog_3", "g6_sog_4", "g6_sog_5"])  # 3-5 (round 6): the Catalina outline, a concave outline
+@pytest.mark.parametrize("name", ["g6_sog_0", "g6_sog_1", "g6_sog_2", "g6_sog_3", "g6_sog_4", "g6_sog_5",  # 3-5 (round 6): the Catalina outline, a concave outline
+                                  "g6_sog_o256", "g6_sog_o257_catalina", "g6_sog_o600"])  # 256 obstacles and past them
 def test_astar_fixlen_sog(name):
     from auv_sim_amd.astar_fixLenSOG import astar
     g = np.load(os.path.join(GOLDEN, name + ".npz"))

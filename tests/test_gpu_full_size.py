@@ -152,10 +152,24 @@ def test_planner_rrt_config4(ctx, orc):
 
 
 def test_astar_config3(ctx, orc):
+    _astar_config3(ctx, 64, (2.0, 6.0))
+
+
+@pytest.mark.parametrize("n_obstacles,radii", [(256, (0.5, 2.5)), (600, (0.5, 2.0))])
+def test_astar_config3_at_the_metric_obstacle_counts(ctx, orc, n_obstacles, radii):
+    """config 3 on the metric's 256-obstacle world (a full LDS obstacle table in the kernel) and past it (the collision tests
+    read the obstacles from memory).  The limit-300 searches never finish in this world, whatever its obstacles; nearly all
+    the others find a path"""
+    a, limits = _astar_config3(ctx, n_obstacles, radii)
+    found = np.array([x["found"] for x in a])
+    assert found[limits <= 200.0].mean() >= 0.75
+
+
+def _astar_config3(ctx, n_obstacles, radii):
     from auv_sim_amd import _astar_lib, synth
     from oracle import orc_astar as oa
     n_inst = 1024
-    w = synth.make_world(seed=12, n_obstacles=64, obst_radius=(2.0, 6.0), n_habitats=10, hab_radius=(10.0, 25.0))
+    w = synth.make_world(seed=12, n_obstacles=n_obstacles, obst_radius=radii, n_habitats=10, hab_radius=(10.0, 25.0))
     ctx.set_world(w["obstacles"], w["habitats"], w["polygon"], w["bins"], w["cells"], w["prob"])
     rng = np.random.default_rng(3)
     starts = np.column_stack([-290.0 + 10.0 * rng.integers(0, 19, n_inst), -90.0 + 10.0 * rng.integers(0, 19, n_inst)])
@@ -178,6 +192,7 @@ def test_astar_config3(ctx, orc):
                    velocity=1.0, cap_nodes=20000, kind="portable")
         assert (a[e]["found"], a[e]["n_nodes"], a[e]["n_children"]) == (o["found"], o["n_nodes"], o["n_children"])
         assert np.array_equal(a[e]["path"], o["path"]) and np.array_equal(a[e]["cost_list"], o["cost_list"])
+    return a, limits
 
 
 def test_particle_filters_at_scale(ctx, orc):

@@ -55,3 +55,31 @@ def test_astar_matches_reference(orc, path, kind):
     g = np.load(path)
     v, kw = astar_kwargs(g)
     check_result(oa.run(v, g["start"], kind=kind, **kw), g)
+
+
+def result_key(r):
+    """what a search returned, as one comparable tuple (two searches differ when their keys do)"""
+    return (r["status"], r["found"], r["n_nodes"], r["n_children"], r["expansions"].tobytes(), r["path"].tobytes(),
+            r["cost_list"].tobytes(), r["smooth_path"].tobytes(), r["hab_left"].tobytes(), r["visited_count"])
+
+
+LDS_OBST = 256  # astar_kernel.h ASTAR_LDS_OBST: larger lists stay in memory
+LARGE = [p for p in FILES if len(np.load(p)["obstacles"]) >= LDS_OBST]
+
+
+@pytest.mark.parametrize("path", LARGE, ids=[os.path.basename(p)[:-4] for p in LARGE])
+def test_large_obstacle_goldens_depend_on_their_tail(orc, path):
+    """the goldens at and past the kernel's LDS obstacle limit (make_golden.py g6o) only pin that branch if their result
+    depends on the obstacles a kernel could drop: the first 256 alone, and (at 256 and 257) the list without its last one,
+    give another search"""
+    from oracle import orc_astar as oa
+    g = np.load(path)
+    v, kw = astar_kwargs(g)
+    full = oa.run(v, g["start"], kind="portable", **kw)
+    check_result(full, g)
+    n = len(g["obstacles"])
+    cuts = ([n - 1] if n <= LDS_OBST + 1 else []) + ([LDS_OBST] if n > LDS_OBST else [])
+    assert cuts
+    for m in cuts:
+        cut = oa.run(v, g["start"], kind="portable", **dict(kw, obstacles=g["obstacles"][:m]))
+        assert result_key(cut) != result_key(full), m
