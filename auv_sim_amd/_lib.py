@@ -44,6 +44,8 @@ SUMMARY_DTYPE = np.dtype([("status", "<i4"), ("n_nodes", "<i4"), ("n_points", "<
 assert SUMMARY_DTYPE.itemsize == C.sizeof(RRTSummary)
 
 MODES = {"timebin": 0, "plantime": 1, "nn": 2}
+# auvp_rrt_episode (include/auvplan.h): one episode's own horizon and habitat list (bit h = habitat h of the world's table)
+EPISODE_DTYPE = np.dtype([("max_traj_time", "<f8"), ("habitat_keep", "<u8")])
 FLAG_ITER_LOG, FLAG_LEAF_LOG, FLAG_PHASE_CLOCKS = 1, 2, 4
 OK, NO_QUALIFYING_LEAF = 0, 1
 
@@ -94,6 +96,8 @@ def load():
     L.auvp_rrt_explore_batch.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(RRTParams), C.c_int32]
     L.auvp_rrt_prepare.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(RRTParams), C.c_int32]
     L.auvp_rrt_prepare_states.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint32), _ip, C.POINTER(RRTParams), C.c_int32]
+    L.auvp_rrt_prepare_episodes.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _ip,
+                                            C.POINTER(RRTParams), C.c_void_p, C.c_int32]
     L.auvp_world_set_habitats.argtypes = [vp, _dp, C.c_int32]
     L.auvp_rrt_run.argtypes = [vp]
     L.auvp_rrt_paths_dev.argtypes = [vp, C.POINTER(C.c_int64), C.c_void_p]
@@ -147,6 +151,33 @@ def _f64(a, shape=None):
 
 def _p(a, t=_dp):
     return a.ctypes.data_as(t)
+
+
+def episode_limits(n_episodes, max_traj_time, habitat_keep, n_habitats, mode="timebin", iter_log=False, phase_clocks=False):
+    """The per-episode limits of a batch (auvp_rrt_prepare_episodes): max_traj_time a number or [E], habitat_keep None (every
+    habitat) or [E] bit masks over the world's habitat table.  Returns (cap = the largest horizon, [E] EPISODE_DTYPE records);
+    raises ValueError on what the library refuses: another mode than time-bin, the iteration log or phase clocks, a horizon
+    that is not > 0, a bit at or above n_habitats."""
+    E = int(n_episodes)
+    if mode != "timebin":
+        raise ValueError("per-episode limits need time-bin mode, not %r" % (mode,))
+    if iter_log or phase_clocks:
+        raise ValueError("per-episode limits: no iteration log or phase clocks (the leaf log is allowed)")
+    mtt = np.broadcast_to(np.asarray(max_traj_time, dtype=np.float64), (E,))
+    if not np.all(mtt > 0) or not np.all(np.isfinite(mtt)):
+        raise ValueError("every max_traj_time must be finite and > 0")
+    allowed = (1 << int(n_habitats)) - 1 if n_habitats < 64 else (1 << 64) - 1
+    if habitat_keep is None:
+        keep = [allowed] * E
+    else:
+        keep = [int(k) for k in np.broadcast_to(np.asarray(habitat_keep, dtype=object), (E,))]
+    for e, k in enumerate(keep):
+        if k < 0 or k & ~allowed:
+            raise ValueError("episode %d: habitat_keep 0x%x names habitats outside the table of %d" % (e, k, n_habitats))
+    rec = np.zeros(E, dtype=EPISODE_DTYPE)
+    rec["max_traj_time"] = mtt
+    rec["habitat_keep"] = np.array(keep, dtype=np.uint64)
+    return float(mtt.max()), rec
 
 
 class Context:
@@ -221,9 +252,10 @@ class Context:
     # ---- RRT.exploring batch ----
     def rrt_explore_batch(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,
                           max_traj_time=500.0, weights=(-3, -3, -4), dist_to_end=2, diff_max=0.5, min_dist=0.5,
-                          max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False):
+                          max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False,
+                          habitat_keep=None):
         self.rrt_prepare(init, seeds, n_iter, mode, freq, bin_interval, v, max_traj_time, weights, dist_to_end,
-                         diff_max, min_dist, max_plan_time, points_per_iter, iter_log, leaf_log, phase_clocks)
+                         diff_max, min_dist, max_plan_time, points_per_iter, iter_log, leaf_log, phase_clocks, habitat_keep)
         self.rrt_run()
         return self.summaries()
 
@@ -233,9 +265,16 @@ class Context:
 
     def rrt_prepare(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,
                     max_traj_time=500.0, weights=(-3, -3, -4), dist_to_end=2, diff_max=0.5, min_dist=0.5,
-                    max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False):
+                    max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False,
+                    habitat_keep=None):
+        """max_traj_time [E] and / or habitat_keep [E] (bit masks over the world's habitat table): every episode plans with its
+        own horizon and habitat list (auvp_rrt_prepare_episodes; the cap is the largest horizon).  Without both: one horizon."""
         init = _f64(init, (-1, 6))
         E = len(init)
+        lim = None
+        if habitat_keep is not None or np.ndim(max_traj_time) > 0:
+            max_traj_time, lim = episode_limits(E, max_traj_time, habitat_keep, self.world_sizes.get("H", 0), mode, iter_log,
+                                                phase_clocks)
         states = None
         if isinstance(seeds, tuple):  # (mt [E,624] uint32, index [E]) as random.getstate() reports
             states = np.ascontiguousarray(np.asarray(seeds[0], dtype=np.uint32).reshape(E, 624))
@@ -250,7 +289,12 @@ class Context:
             p.w[i] = float(weights[i])
         p.mode, p.max_iter, p.points_per_iter = MODES[mode], int(n_iter), float(points_per_iter)
         flags = (FLAG_ITER_LOG if iter_log else 0) | (FLAG_LEAF_LOG if leaf_log else 0) | (FLAG_PHASE_CLOCKS if phase_clocks else 0)
-        if states is not None:
+        if lim is not None:
+            self._chk(self.L.auvp_rrt_prepare_episodes(
+                self.h, E, _p(init), None if states is not None else seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                states.ctypes.data_as(C.POINTER(C.c_uint32)) if states is not None else None,
+                _p(sidx, _ip) if states is not None else None, C.byref(p), lim.ctypes.data_as(C.c_void_p), flags))
+        elif states is not None:
             self._chk(self.L.auvp_rrt_prepare_states(self.h, E, _p(init), states.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                      _p(sidx, _ip), C.byref(p), flags))
         else:
@@ -386,7 +430,8 @@ class Context:
         return int(self.L.auvp_rrt_last_stream_len(self.h))
 
     def last_rrt_kernel(self):
-        """name of the expansion kernel the last rrt_run launched (rrt_rows_kernel / rrt_explore_kernel / rrt_duo_kernel)"""
+        """name of the expansion kernel the last rrt_run launched (rrt_rows_kernel / rrt_explore_kernel / rrt_duo_kernel /
+        rrt_explore_lim_kernel)"""
         return (self.L.auvp_rrt_last_kernel(self.h) or b"").decode()
 
     def last_leaf_stats(self):

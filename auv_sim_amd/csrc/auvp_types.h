@@ -98,6 +98,16 @@ struct RrtParamsDev {
   double inv_bin_interval;  // RN(1 / bin_interval): first guess of t // bin_interval (corrected exactly by the remainder)
 };
 
+// Per-episode limits of a batch prepared by auvp_rrt_prepare_episodes (RRT.replanning_batch): the episode's own horizon,
+// its number of time bins K = ceil(max_traj_time / bin_interval) and the habitats of the world's table it still plans for
+// (bit h = habitat h; the others count as absent from its list).  Read by rrt_explore_lim_kernel / rrt_leaf_lim_kernel
+// through a kernel argument of their own: a new RrtBuffers field would move the kernel arguments of every other kernel.
+struct RrtEpisodeLimDev {
+  double max_traj_time;
+  unsigned long long keep;
+  int32_t K, _pad;
+};
+
 struct RrtSummary {  // must match auvp_rrt_summary in include/auvplan.h
   int32_t status, n_nodes, n_points, n_leaves, best_leaf, best_path_len, iters_run, n_candidates;
   double best_cost[4];

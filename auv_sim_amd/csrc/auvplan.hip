@@ -105,6 +105,11 @@ struct auvp_handle {
   DevBuf d_nodes_f, d_nodes_i, d_points, d_bin_items, d_bin_count, d_mt, d_mtidx, d_seeds, d_init, d_summary, d_itlog_i, d_itlog_b,
       d_leaf_c, d_leaf_i, d_phase, d_leaf_stats, d_node_c, d_node_q, d_node_xy, d_tmp0, d_tmp1, d_tmp2, d_tmp3, d_tmp4, d_tmp5, d_stream;
   bool have_batch = false, prepared = false;
+  // per-episode limits (auvp_rrt_prepare_episodes): the batch runs rrt_explore_lim_kernel + rrt_leaf_lim_kernel; lim_K: every
+  // episode's own K (P.K is the cap's)
+  bool lim = false;
+  DevBuf d_lim;
+  std::vector<int32_t> lim_K;
   double last_ms = 0.0;
   int last_grid = 0, last_block = 0, last_lds = 0;
   // planner families that live in their own headers keep their state behind an opaque pointer
@@ -663,7 +668,7 @@ int auvp_rrt_explore_batch(auvp_handle* h, int32_t E, const double* init, const 
 }
 
 static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds, const uint32_t* states,
-                            const int32_t* state_index, const auvp_rrt_params* p, int32_t flags);
+                            const int32_t* state_index, const auvp_rrt_params* p, int32_t flags, bool lim = false);
 
 int auvp_rrt_prepare(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds,
                      const auvp_rrt_params* p, int32_t flags) {
@@ -677,9 +682,46 @@ int auvp_rrt_prepare_states(auvp_handle* h, int32_t E, const double* init, const
   return rrt_prepare_impl(h, E, init, nullptr, mt, mt_index, p, flags);
 }
 
-static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds, const uint32_t* states,
-                            const int32_t* state_index, const auvp_rrt_params* p, int32_t flags) {
+int auvp_rrt_prepare_episodes(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds, const uint32_t* mt,
+                              const int32_t* mt_index, const auvp_rrt_params* p, const auvp_rrt_episode* episodes, int32_t flags) {
   if (!h) return AUVP_ERR_ARG;
+  if (E <= 0 || !init || !p || !episodes) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
+  if (!seeds && (!mt || !mt_index)) return fail(h, AUVP_ERR_ARG, "neither seeds nor mt states");
+  if (p->mode != AUVP_MODE_TIMEBIN) return fail(h, AUVP_ERR_ARG, "per-episode limits need time-bin mode");
+  if (flags & (AUVP_FLAG_ITER_LOG | AUVP_FLAG_PHASE_CLOCKS)) return fail(h, AUVP_ERR_ARG, "per-episode limits: no iteration log / phase clocks");
+  if (!(p->bin_interval > 0)) return fail(h, AUVP_ERR_ARG, "bin_interval <= 0");
+  if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
+  const int H = h->W.n_habitats;
+  const uint64_t all = H >= 64 ? ~0ull : ((1ull << H) - 1ull);
+  std::vector<RrtEpisodeLimDev> lim((size_t)E);
+  std::vector<int32_t> ks((size_t)E);
+  for (int e = 0; e < E; e++) {
+    const double t = episodes[e].max_traj_time;
+    if (!(t > 0.0 && t <= p->max_traj_time))
+      return fail(h, AUVP_ERR_ARG, "episode %d: max_traj_time %g outside (0, %g]", e, t, p->max_traj_time);
+    if (episodes[e].habitat_keep & ~all) return fail(h, AUVP_ERR_ARG, "episode %d: habitat_keep names habitats >= %d", e, H);
+    lim[e].max_traj_time = t;
+    lim[e].keep = episodes[e].habitat_keep;
+    lim[e].K = ks[e] = (int)std::ceil(t / p->bin_interval);  // <= the cap's K (ceil is monotone)
+    lim[e]._pad = 0;
+  }
+  int rc = rrt_prepare_impl(h, E, init, seeds, seeds ? nullptr : mt, seeds ? nullptr : mt_index, p, flags, true);
+  if (rc != AUVP_OK) return rc;
+  // the batch is prepared only with its limits on the device: a failed upload leaves nothing a later auvp_rrt_run could launch
+  // (it would run every episode at the cap's horizon with the whole habitat list)
+  h->prepared = false;
+  if ((rc = upload(h, h->d_lim, lim.data(), lim.size()))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->prepared = true;
+  h->lim = true;
+  h->lim_K.swap(ks);
+  return AUVP_OK;
+}
+
+static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds, const uint32_t* states,
+                            const int32_t* state_index, const auvp_rrt_params* p, int32_t flags, bool lim) {
+  if (!h) return AUVP_ERR_ARG;
+  h->lim = false;
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   if (E <= 0 || !init || !p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
   if (p->max_iter <= 0 || !(p->freq >= 0) || p->mode < 0 || p->mode > 2) return fail(h, AUVP_ERR_ARG, "bad params");
@@ -702,7 +744,7 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
   if (h->d_stream.p) {
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-    if (!(P.mode == 0 && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true) && h->opt_flag(OPT_ROWS, E > 18 * (n_cu > 0 ? n_cu : 256))))
+    if (lim || !(P.mode == 0 && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true) && h->opt_flag(OPT_ROWS, E > 18 * (n_cu > 0 ? n_cu : 256))))
       h->d_stream.release();
   }
   RrtBuffers& B = h->B;
@@ -887,14 +929,15 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   // 10 240 episodes 737 vs 877.  End of round 6 (the rows kernel has lost a quarter of its instructions since), same batches:
   // 4 096 episodes 631 vs 606, 5 120: 609 vs 647, 6 144: 727 vs 773, 8 192: 715 vs 1 014 -- the crossover is between 16 and 20
   // episodes per CU now: rows above 18 (tools/batch_size_probe.py).  Option ROWS = 1 / 0 forces it on (limits permitting) / off.
-  const bool rows_ok = P.mode == 0 && !iter_log && nfreq <= RW_MAX_FREQ && O_ <= RW_MAX_OBST && P.max_iter < 65534 &&
+  // (a batch with per-episode limits runs rrt_explore_lim_kernel, whatever the options say)
+  const bool rows_ok = !h->lim && P.mode == 0 && !iter_log && nfreq <= RW_MAX_FREQ && O_ <= RW_MAX_OBST && P.max_iter < 65534 &&
                        rp.total <= 160 * 1024;
   const bool use_rows = rows_ok && h->opt_flag(OPT_ROWS, E > 18 * n_cu_);
   int grid_used = grid, block_used = xw * 64, lds_used = (int)lds;
   bool stream_launched = false;
   // latency runs (at most four episodes per CU: one episode, config 2's 1 024 replicas): two wavefronts per episode
   // (rrt_duo_kernel.h).  Option DUO = 1 / 0 forces it on (limits permitting) / off.
-  const bool duo_ok = P.mode == 0 && !diag && nfreq <= DUO_MAX_FREQ && nfreq >= 1 && O_ <= 256 && h->max_pts <= 64;
+  const bool duo_ok = !h->lim && P.mode == 0 && !diag && nfreq <= DUO_MAX_FREQ && nfreq >= 1 && O_ <= 256 && h->max_pts <= 64;
   // Measured (tools/duo_probe.py, M expansions/s one vs two wavefronts per episode): 1 episode 0.25 vs 0.32, 256: 62 vs 80,
   // 1 024: 227 vs 271 (config 2's replicas, 64 obstacles: 241 vs 283), 2 048: 409 vs 435, 4 096: 621 vs 485
   const bool use_duo = duo_ok && !use_rows && !one_wave_only && h->opt_flag(OPT_DUO, E <= 8 * n_cu_);
@@ -904,6 +947,7 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   // Option TRIO = 1 / 0 forces it on (limits permitting) / off; an explicit DUO = 1 takes precedence.
   const bool use_trio = duo_ok && !use_rows && !one_wave_only && h->opt_flag(OPT_TRIO, E <= TRIO_EP * n_cu_ && !h->opt_on(OPT_DUO));
   h->last_rrt_kernel = use_rows ? "rrt_rows_kernel" : (use_trio ? "rrt_trio_kernel" : (use_duo ? "rrt_duo_kernel" : "rrt_explore_kernel"));
+  if (h->lim) h->last_rrt_kernel = "rrt_explore_lim_kernel";
   h->last_stream_ms = 0.0;
   h->last_stream_len = 0;
   if (use_trio) {
@@ -1009,9 +1053,17 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   } else {
   // compile-time specialisation: obstacles per lane (J), parent-sampling mode, diagnostics on/off
   const int jsel = O <= 64 ? 0 : (O <= 128 ? 1 : (O <= 256 ? 2 : (O <= 512 ? 3 : 4)));
+  const RrtEpisodeLimDev* lim = h->d_lim.as<RrtEpisodeLimDev>();
+  auto launch_lim = [&](auto kern) -> hipError_t {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(xw * 64), lds, h->stream, h->W, PR, B, (int)E, h->max_pts, lim);
+    return hipGetLastError();
+  };
 #define AUVP_LAUNCH_J(JV)                                                                   \
   do {                                                                                      \
-    if (P.mode == 0) le = diag ? launch(rrt_explore_kernel<JV, 0, true>) : launch(rrt_explore_kernel<JV, 0, false>); \
+    if (h->lim) le = launch_lim(rrt_explore_lim_kernel<JV>);                                \
+    else if (P.mode == 0) le = diag ? launch(rrt_explore_kernel<JV, 0, true>) : launch(rrt_explore_kernel<JV, 0, false>); \
     else if (P.mode == 1) le = diag ? launch(rrt_explore_kernel<JV, 1, true>) : launch(rrt_explore_kernel<JV, 1, false>); \
     else le = diag ? launch(rrt_explore_kernel<JV, 2, true>) : launch(rrt_explore_kernel<JV, 2, false>); \
   } while (0)
@@ -1034,14 +1086,21 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
     // (option LEAF_SWEEP_ALL: no pruning, every node visited -- what trees of more than 131 072 nodes get; for tests)
     const int bm_words = h->opt_on(OPT_LEAF_SWEEP_ALL) ? 0 : rrt_leaf_mark_words(B.cap_nodes);
     const int dyn = gl + RRT_LEAF_WAVES * bm_words * 4;
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(rrt_leaf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
-    hipLaunchKernelGGL(rrt_leaf_kernel, dim3((E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES), dim3(RRT_LEAF_WAVES * 64), dyn, h->stream,
-                       h->W, P, B, (int)E, bm_words);
+    if (h->lim) {
+      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(rrt_leaf_lim_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
+      hipLaunchKernelGGL(rrt_leaf_lim_kernel, dim3((E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES), dim3(RRT_LEAF_WAVES * 64), dyn, h->stream,
+                         h->W, P, B, (int)E, bm_words, h->d_lim.as<RrtEpisodeLimDev>());
+    } else {
+      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(rrt_leaf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
+      hipLaunchKernelGGL(rrt_leaf_kernel, dim3((E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES), dim3(RRT_LEAF_WAVES * 64), dyn, h->stream,
+                         h->W, P, B, (int)E, bm_words);
+    }
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   // (the most 32-bit outputs one episode drew: eight bytes into the mapped page beside the pipeline flag)
-  const bool want_drawn = B.leaf_stats && h->pipe_fail_host;
+  // (not from a batch with per-episode limits: the figure sizes streams of plain batches with the same parameter block)
+  const bool want_drawn = B.leaf_stats && h->pipe_fail_host && !h->lim;
   if (want_drawn) HIPCHK(h, hipMemcpyAsync(h->pipe_fail_host + 2, B.leaf_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (want_drawn && !h->pipe_failed()) {
@@ -1232,10 +1291,10 @@ int auvp_rrt_bin_sizes(auvp_handle* h, int32_t ep, int32_t* sizes, int32_t* n_bi
   if (!h) return AUVP_ERR_ARG;
   if (!h->have_batch || ep < 0 || ep >= h->E) return fail(h, AUVP_ERR_STATE, "bad episode");
   HIPCHK(h, hipSetDevice(h->device));
-  const int K = h->P.K;
+  const int K = h->lim ? h->lim_K[(size_t)ep] : h->P.K;  // (per-episode limits: the episode's own K; the rows are the cap's)
   if (n_bins) *n_bins = K;
   if (sizes && K > 0)
-    HIPCHK(h, hipMemcpy(sizes, h->B.bin_count + (size_t)ep * (K + 1) + 1, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sizes, h->B.bin_count + (size_t)ep * (h->P.K + 1) + 1, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
   return AUVP_OK;
 }
 

@@ -59,12 +59,58 @@ def pack_shark_grid(sharkGrid):
     return bins, cells, prob.reshape(len(keys), len(cell_keys))
 
 
+def habitat_keep_bits(masks, n_habitats, n_episodes):
+    """exploring_batch's habitat_masks -> [E] ints (bit h: habitats[h] is on the episode's list): None (all of them), [E] ints,
+    or [E, H] booleans"""
+    if masks is None:
+        return [(1 << n_habitats) - 1] * n_episodes
+    a = np.asarray(masks)
+    if a.dtype == bool:
+        a = a.reshape(n_episodes, n_habitats)
+        return [sum(1 << h for h in range(n_habitats) if row[h]) for row in a]
+    return [int(m) for m in masks]
+
+
+def first_bucket_commit(course_t, course_xy, t0, max_traj_time, round_span, keep, habitats_xys):
+    """One round of replanning's host step (rrt_dubins.py:82-87) on arrays: the points of the course that splitPath
+    (:590-602) puts into its first bucket, and removeHabitat (:604-610) applied to the episode's habitat list given as the
+    bit mask `keep` over the table habitats_xys [H,3] (list order = table order).  Returns (boolean mask of the course's
+    points in the first bucket, the new keep).  Raises ValueError where the reference's next(iter(buckets)) would raise:
+    the horizon holds no whole bucket."""
+    if math.floor(max_traj_time / round_span) < 1:
+        raise ValueError("max_traj_time %r holds no shark-interval bucket of %r" % (max_traj_time, round_span))
+    lo, hi = t0 + 0 * round_span, t0 + (0 + 1) * round_span  # splitPath's first edge, the same float operations
+    t = np.asarray(course_t, dtype=np.float64)
+    sel = (lo <= t) & (t <= hi)
+    if keep and len(habitats_xys):
+        hb = np.asarray(habitats_xys, dtype=np.float64).reshape(-1, 3)
+        xy = np.asarray(course_xy, dtype=np.float64).reshape(-1, 2)[sel]
+        # math.sqrt((x - hx) ** 2 + (y - hy) ** 2) <= size per (point, habitat): every habitat that contains each point
+        dx, dy = xy[:, None, 0] - hb[None, :, 0], xy[:, None, 1] - hb[None, :, 1]
+        inside = np.sqrt(dx * dx + dy * dy) <= hb[None, :, 2]
+        bits = inside.astype(object) @ np.array([1 << h for h in range(len(hb))], dtype=object) if len(xy) else []
+        for b in bits:  # point by point: the first habitat still on the list is removed
+            m = int(b) & keep
+            if m:
+                keep &= ~(m & -m)
+    return sel, keep
+
+
 def _mt_state_of(rng_state):
     """random.getstate() -> (624 words, index)"""
     ver, internal, _ = rng_state
     if ver != 3 or len(internal) != 625:
         raise RuntimeError("unexpected random.getstate() layout")
     return np.array(internal[:624], dtype=np.uint32), int(internal[624])
+
+
+class _Init:
+    """a committed state as exploring reads it (x, y, theta, traj_time_stamp, plan_time_stamp, length)"""
+    __slots__ = ("x", "y", "theta", "traj_time_stamp", "plan_time_stamp", "length")
+
+    def __init__(self, row):
+        self.x, self.y, self.theta, self.traj_time_stamp, self.plan_time_stamp, self.length = (
+            row[0], row[1], row[2], row[4], row[5], row[6])
 
 
 class RRT:
@@ -108,17 +154,16 @@ class RRT:
 
     def exploring_batch(self, initials, habitats, plot_interval, bin_interval, v, shark_interval,
                         traj_time_stamp=False, max_plan_time=5, max_traj_time=200.0, plan_time=True,
-                        weights=[-1, -1, -1], max_iter=None, seeds=None):
+                        weights=[-1, -1, -1], max_iter=None, seeds=None, habitat_masks=None):
         """E independent exploring() calls in one launch (one wavefront per episode).  Returns a list of
-        result dicts (None where the reference would have raised for lack of a qualifying leaf)."""
+        result dicts (None where the reference would have raised for lack of a qualifying leaf).
+
+        Per-episode limits (time-bin mode): max_traj_time [E] gives every episode its own horizon, habitat_masks ([E] ints,
+        bit h = habitats[h], or [E, H] booleans) its own habitat list -- the subsequence of `habitats` its mask selects.
+        Episode e then equals exploring(initials[e], [its habitats], ..., max_traj_time=max_traj_time[e])."""
         E = len(initials)
         if max_iter is None:
             max_iter = max(1, int(math.ceil(max_plan_time * self.iters_per_second)))
-        mode = "timebin" if (plan_time and traj_time_stamp) else ("plantime" if plan_time else "nn")
-        hab = _circles(habitats)
-        self._ctx.set_habitats(hab)
-        init = np.array([[float(m.x), float(m.y), float(m.theta), float(m.traj_time_stamp),
-                          float(m.plan_time_stamp), float(m.length)] for m in initials], dtype=np.float64)
         use_global = seeds is None
         if use_global:
             if E != 1:
@@ -127,10 +172,8 @@ class RRT:
             seed_arg = (words.reshape(1, 624), np.array([idx], dtype=np.int32))
         else:
             seed_arg = np.array([int(s) for s in seeds], dtype=np.uint64)
-        summ = self._ctx.rrt_explore_batch(init, seed_arg, int(max_iter), mode=mode, freq=self.freq,
-                                           bin_interval=bin_interval, v=v, max_traj_time=max_traj_time,
-                                           weights=weights, dist_to_end=self.dist_to_end, diff_max=self.diff_max,
-                                           min_dist=0.5, max_plan_time=float(max_iter))  # virtual clock: 1 tick per iteration
+        summ = self._explore_summaries(initials, habitats, bin_interval, v, traj_time_stamp, max_traj_time, plan_time, weights,
+                                       max_iter, seed_arg, habitat_masks)
         if use_global:
             n = int(summ[0]["n_draw32"])
             if n:
@@ -144,6 +187,7 @@ class RRT:
         self._last = (summ, list(initials))
         self._mps_cache = None
         self.t_start = 0.0
+        horizons = np.broadcast_to(np.asarray(max_traj_time, dtype=np.float64), (E,))
         out = []
         for e in range(E):
             s = summ[e]
@@ -151,10 +195,28 @@ class RRT:
                 out.append(None)
                 continue
             course = self._materialise_course(paths[e], initials[e])
-            split = self.splitPath(course, shark_interval, [initials[e].traj_time_stamp, max_traj_time])
+            mtt = max_traj_time if np.ndim(max_traj_time) == 0 else float(horizons[e])
+            split = self.splitPath(course, shark_interval, [initials[e].traj_time_stamp, mtt])
             c = [float(x) for x in s["best_cost"]]
             out.append({"path length": float(s["best_length"]), "path": [course, split], "cost": [c[0], c[1:]]})
         return out
+
+    def _explore_summaries(self, initials, habitats, bin_interval, v, traj_time_stamp, max_traj_time, plan_time, weights,
+                           max_iter, seed_arg, habitat_masks=None):
+        """one prepare + run of exploring episodes on this object's context; the summaries (statuses unchecked)"""
+        mode = "timebin" if (plan_time and traj_time_stamp) else ("plantime" if plan_time else "nn")
+        hab = _circles(habitats)
+        self._ctx.set_habitats(hab)
+        init = np.array([[float(m.x), float(m.y), float(m.theta), float(m.traj_time_stamp),
+                          float(m.plan_time_stamp), float(m.length)] for m in initials], dtype=np.float64).reshape(-1, 6)
+        keep = None
+        if habitat_masks is not None or np.ndim(max_traj_time) > 0:  # per-episode limits
+            keep = np.array(habitat_keep_bits(habitat_masks, len(hab), len(init)), dtype=np.uint64)
+        return self._ctx.rrt_explore_batch(init, seed_arg, int(max_iter), mode=mode, freq=self.freq,
+                                           bin_interval=bin_interval, v=v, max_traj_time=max_traj_time,
+                                           weights=weights, dist_to_end=self.dist_to_end, diff_max=self.diff_max,
+                                           min_dist=0.5, max_plan_time=float(max_iter),  # virtual clock: 1 tick per iteration
+                                           habitat_keep=keep)
 
     def replanning(self, start, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
                    max_iter=None, seed=None):
@@ -194,6 +256,125 @@ class RRT:
         total = habitat_shark_cost_func(committed[1:], committed[-1].traj_time_stamp, all_habitats, self.sharkGrid,
                                         weight=[-3, -3, -4], device_context=self._cost_ctx)
         return [committed[1:], rounds, total]
+
+    def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
+                         max_iter=None, seeds=None, rngs=None, as_arrays=False):
+        """N independent replanning() loops, one exploring launch per round over the AUVs still planning (per-episode
+        limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
+        replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
+        seeds[e]) it equals the call that continues the global stream in that generator's state, and the generator is
+        advanced as exploring advances the global stream.  The caller's `habitats` list is not changed: every entry carries
+        its own list of the habitats left.  An AUV whose call would raise TypeError (no qualifying leaf) gets None.
+
+        Returns a list of [committed trajectory, {round: [bucket, habitats at that round]}, cost, habitats left]
+        (Motion_plan_state objects and the caller's habitat objects; the first three as replanning returns them) or, with as_arrays=True, of dicts of numpy arrays: traj [n,7] (x, y, theta, v, traj_time_stamp,
+        plan_time_stamp, length), round_len [R], round_keep [R] (habitat bit masks at each round), round_max_traj_time [R],
+        round_cost [R,4], keep (the habitats left), cost [4].  The SharkUpdate that replanning leaves in self.sharkEstimate
+        is not built (nothing reads it)."""
+        N = len(starts)
+        horizon_end = list(self.sharkGrid.keys())[-1][1]
+        round_span = plan_time_budget + replan_time_interval
+        all_habitats = list(habitats)
+        hab = _circles(all_habitats)
+        H = len(all_habitats)
+        if max_iter is None:
+            max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
+        gens = [None] * N     # rngs[e]: the global stream of a sequential call
+        streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
+        for e in range(N):
+            if rngs is not None and rngs[e] is not None:
+                gens[e] = rngs[e]
+            elif seeds is not None and seeds[e] is not None:
+                streams[e] = random.Random(seeds[e])
+            else:
+                raise ValueError("AUV %d has neither a seed nor a generator" % e)
+        keep = [(1 << H) - 1] * N
+        ttl = [float(traj_time_length)] * N
+        last = [[float(m.x), float(m.y), float(m.theta), float(getattr(m, "v", 0.0) or 0.0), float(m.traj_time_stamp),
+                 float(m.plan_time_stamp), float(m.length)] for m in starts]
+        last_obj = list(starts)
+        traj = [[] for _ in range(N)]      # committed rows (arrays) or objects
+        rounds = [[] for _ in range(N)]    # (bucket, keep at that round, max_traj_time, best_cost)
+        alive = [True] * N
+        while True:
+            act = [e for e in range(N) if alive[e] and last[e][4] + round_span < horizon_end]
+            if not act:
+                break
+            for e in act:
+                if ttl[e] + last[e][4] > horizon_end:  # stays clipped for the later rounds too (:76-77)
+                    ttl[e] = horizon_end - last[e][4]
+            mtt = np.array([ttl[e] + last[e][4] for e in act], dtype=np.float64)
+            round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
+            if all(gens[e] is None for e in act):
+                seed_arg = np.array([round_seeds[e] for e in act], dtype=np.uint64)
+            else:
+                st = [_mt_state_of(gens[e].getstate() if gens[e] is not None else random.Random(round_seeds[e]).getstate())
+                      for e in act]
+                seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
+            init_objs = [_Init(last[e]) for e in act]
+            summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, mtt, True, weight, max_iter, seed_arg,
+                                           [keep[e] for e in act])
+            for i, e in enumerate(act):
+                n = int(summ[i]["n_draw32"])
+                if gens[e] is not None and n:
+                    gens[e].getrandbits(32 * n)  # what exploring does to the global stream
+            bad = summ["status"] < 0
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise _lib.AuvpError(int(summ[i]["status"]), "AUV %d failed on the device (status %d)" % (act[i], int(summ[i]["status"])))
+            paths = self._ctx.paths(summ)
+            for i, e in enumerate(act):
+                if summ[i]["status"] == _lib.NO_QUALIFYING_LEAF:
+                    alive[e] = False
+                    traj[e] = None
+                    continue
+                p = paths[i].copy()
+                p[0] = last[e]  # the course starts at the committed state itself (exploring returns the caller's object)
+                sel, new_keep = first_bucket_commit(p[:, 4], p[:, :2], last[e][4], float(mtt[i]), round_span, keep[e], hab)
+                bucket = p[sel]
+                if as_arrays:
+                    traj[e].append(bucket)
+                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(summ[i]["best_cost"])))
+                else:
+                    course = self._materialise_course(paths[i], last_obj[e])
+                    objs = [course[j] for j in np.flatnonzero(sel)]
+                    traj[e].extend(objs)
+                    rounds[e].append((objs, [all_habitats[h] for h in range(H) if (keep[e] >> h) & 1]))
+                    if objs:
+                        last_obj[e] = objs[-1]
+                keep[e] = new_keep
+                if len(bucket):
+                    last[e] = [float(x) for x in bucket[-1]]
+        # the whole trajectory's cost against the ORIGINAL list (:192-195), every AUV in one launch
+        if self._cost_ctx is None:
+            self._cost_ctx = _lib.Context(self._ctx.device)
+        done = [e for e in range(N) if traj[e] is not None]
+        costs = {}
+        if done:
+            rows = {e: (np.concatenate(traj[e]) if as_arrays and traj[e] else
+                        np.array([[m.x, m.y, m.theta, m.v, m.traj_time_stamp, m.plan_time_stamp, m.length] for m in traj[e]],
+                                 dtype=np.float64).reshape(-1, 7)) for e in done}
+            self._cost_ctx.set_world(None, hab, None, self._bins, self._cells, self._prob)
+            out = self._cost_ctx.cost_paths([rows[e][:, [0, 1, 4]] for e in done], [0] * len(done), [len(self._bins)] * len(done),
+                                            [float(rows[e][-1, 4]) if len(rows[e]) else float(last[e][4]) for e in done],
+                                            [[-3.0, -3.0, -4.0]] * len(done))
+            costs = {e: out[i] for i, e in enumerate(done)}
+        res = []
+        for e in range(N):
+            if traj[e] is None:
+                res.append(None)
+            elif as_arrays:
+                r = rounds[e]
+                res.append(dict(traj=rows[e], round_len=np.array([x[0] for x in r], dtype=np.int64),
+                                round_keep=np.array([x[1] for x in r], dtype=np.uint64),
+                                round_max_traj_time=np.array([x[2] for x in r]),
+                                round_cost=np.array([x[3] for x in r]).reshape(-1, 4), keep=keep[e], cost=costs[e]))
+            else:
+                c = costs[e]
+                res.append([traj[e], {k + 1: [b, hl] for k, (b, hl) in enumerate(rounds[e])},
+                            [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
+                            [all_habitats[h] for h in range(H) if (keep[e] >> h) & 1]])
+        return res
 
     # ------------------------------------------------------------------ host-side helpers (reference names)
     def splitPath(self, path, shark_interval, traj_time):

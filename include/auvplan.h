@@ -117,6 +117,21 @@ int auvp_rrt_prepare(auvp_handle* h, int32_t n_episodes, const double* init, con
  * exactly as random.getstate() reports them (drop-in use: the global `random` state) */
 int auvp_rrt_prepare_states(auvp_handle* h, int32_t n_episodes, const double* init, const uint32_t* mt,
                             const int32_t* mt_index, const auvp_rrt_params* params, int32_t flags);
+/* as prepare(), with limits of every episode's own (RRT.replanning_batch: many receding-horizon loops, one
+ * round per batch): episode e plans with the horizon episodes[e].max_traj_time (its own number of time bins
+ * K = ceil(max_traj_time / bin_interval)) and with the habitats of the world's table whose bit is set in
+ * episodes[e].habitat_keep, in table order -- as if that shorter list had been set.  params->max_traj_time is the
+ * cap: 0 < max_traj_time <= cap, and bits at or above n_habitats are refused.  The generators come from seeds [E]
+ * (mt, mt_index NULL) or, with seeds NULL, from mt [E,624] + mt_index [E] as in prepare_states().  Time-bin mode
+ * only; AUVP_FLAG_ITER_LOG and AUVP_FLAG_PHASE_CLOCKS are refused (the leaf log is allowed).  run(), summaries(),
+ * paths(), tree() work unchanged; bin_sizes() reports the episode's own K.  AUVP_ERR_ARG on any of these. */
+typedef struct {
+  double max_traj_time;  /* this episode's horizon (<= params->max_traj_time) */
+  uint64_t habitat_keep; /* bit h: habitat h of the world's table is on this episode's list */
+} auvp_rrt_episode;
+int auvp_rrt_prepare_episodes(auvp_handle* h, int32_t n_episodes, const double* init, const uint64_t* seeds,
+                              const uint32_t* mt, const int32_t* mt_index, const auvp_rrt_params* params,
+                              const auvp_rrt_episode* episodes, int32_t flags);
 int auvp_rrt_run(auvp_handle* h);
 int auvp_rrt_summaries(auvp_handle* h, auvp_rrt_summary* out /* [E] */);
 /* generate_final_course (:321-331) of every episode's best leaf, reversed to root->leaf (:174).
