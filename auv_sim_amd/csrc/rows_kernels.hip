@@ -26,7 +26,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_rrt_rows_launc
 }
 
 // round 6: the random() streams generated ahead (rrt_stream_kernel.h), and the expansion kernel that reads them
-// (rrt_rows_stream_kernel.h: generated from rrt_rows_kernel.h by tools/gen_rows_stream_kernel.py)
+// (rrt_rows_stream_kernel.h: the same body as rrt_rows_kernel's, rrt_rows_body.h, with the generator's calls replaced by stream reads)
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_rrt_stream_launch(const auvp::RrtBuffers* B, int n_episodes, hipStream_t stream) {
   const int grid = (n_episodes + auvp::RSTREAM_WAVES - 1) / auvp::RSTREAM_WAVES;
   hipLaunchKernelGGL(auvp::rrt_stream_kernel, dim3(grid), dim3(auvp::RSTREAM_WAVES * 64), 0, stream, *B, n_episodes);

@@ -312,10 +312,3 @@ def test_a_caller_that_replans_on_a_changing_world_gets_the_stream_from_its_seco
         assert kernels == ["rrt_rows_kernel"] + ["rrt_rows_stream_kernel"] * 5 and redone == 0, (kernels, redone)
     finally:
         ctx.close()
-
-
-def test_the_generated_header_is_what_the_generator_writes():
-    """rrt_rows_stream_kernel.h is generated from rrt_rows_kernel.h (tools/gen_rows_stream_kernel.py): a change to the classic
-    kernel's body that was not carried over fails here"""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_rows_stream_kernel.py"), "--check"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
