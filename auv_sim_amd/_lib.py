@@ -127,6 +127,9 @@ def load():
     L.auvp_rrt_last_stream_ms.restype = C.c_double
     L.auvp_rrt_last_stream_len.argtypes = [vp]
     L.auvp_rrt_last_stream_len.restype = C.c_int64
+    if hasattr(L, "auvp_rrt_last_stream_mirror"):  # (an earlier build loaded through AUVPLAN_LIBRARY for a comparison has neither)
+        L.auvp_rrt_last_stream_mirror.argtypes = [vp]
+        L.auvp_rrt_rows_stream_shape.argtypes = [C.c_int32] * 6 + [_ip, _ip, _ip]
     L.auvp_hbm_probe.argtypes = [vp, C.c_uint64, C.c_int32, _dp, _dp]
     L.auvp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     L.auvp_unset_option.argtypes = [vp, C.c_char_p]
@@ -141,7 +144,7 @@ def load():
 OPTION_NAMES = ("ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
                 "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
                 "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES",
-                "ROWS_WG_WAVES")
+                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR")
 
 
 def _f64(a, shape=None):
@@ -178,6 +181,17 @@ def episode_limits(n_episodes, max_traj_time, habitat_keep, n_habitats, mode="ti
     rec["max_traj_time"] = mtt
     rec["habitat_keep"] = np.array(keep, dtype=np.uint64)
     return float(mtt.max()), rec
+
+
+def rows_stream_shape(K, n_habitats, n_poly, n_bins, waves_wanted=12, force=-1):
+    """the launch the host chooses for rrt_rows_stream_kernel (no GPU needed): (waves per workgroup, mirrored ring?, LDS bytes)
+    for K time bins and a world with these table sizes; force: -1 the host's rule, 0 the masked ring, 1 the mirrored one"""
+    w, m, l = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = load().auvp_rrt_rows_stream_shape(int(K), int(n_habitats), int(n_poly), int(n_bins), int(waves_wanted), int(force),
+                                           C.byref(w), C.byref(m), C.byref(l))
+    if rc != 0:
+        raise AuvpError(rc, "auvp_rrt_rows_stream_shape: bad argument")
+    return w.value, bool(m.value), l.value
 
 
 class Context:
@@ -424,6 +438,11 @@ class Context:
     def last_stream_ms(self):
         """ms of the launch that generated the random numbers ahead of the last rrt_run's expansion kernel (0: it did not)"""
         return float(self.L.auvp_rrt_last_stream_ms(self.h))
+
+    def last_stream_mirror(self):
+        """the LDS ring of the last rrt_run's rrt_rows_stream_kernel: 1 its first entries mirrored behind it, 0 every read masked
+        (-1: another expansion kernel ran)"""
+        return int(self.L.auvp_rrt_last_stream_mirror(self.h))
 
     def last_stream_len(self):
         """random() numbers per episode that launch wrote (0: none)"""

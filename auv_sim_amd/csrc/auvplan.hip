@@ -28,7 +28,7 @@ using namespace auvp;
 // rrt_rows_kernel lives in rows_kernels.hip (a translation unit with its own compiler flags); this is its launcher
 extern "C" hipError_t auvpi_rrt_stream_launch(const auvp::RrtBuffers* B, int n_episodes, hipStream_t stream);
 extern "C" hipError_t auvpi_rrt_rows_stream_launch(const auvp::WorldDev* W, const auvp::RrtParamsDev* P, const auvp::RrtBuffers* B, int n_episodes,
-                                                   int grid, int block, int lds_max, int lds, hipStream_t stream);
+                                                   int grid, int block, int lds_max, int lds, int mirror, hipStream_t stream);
 extern "C" hipError_t auvpi_rrt_rows_launch(const auvp::WorldDev* W, const auvp::RrtParamsDev* P, const auvp::RrtBuffers* B, int n_episodes,
                                             int grid, int block, int lds_max, int lds, hipStream_t stream);
 
@@ -59,12 +59,12 @@ struct DevBuf {
 enum AuvpOpt {
   OPT_ROWS, OPT_DUO, OPT_TRIO, OPT_QUAD, OPT_TIGHT_CULL, OPT_NN_EXACT, OPT_LEAF_SWEEP_ALL, OPT_NO_HABITAT_GRID, OPT_RG_MAX_ENTRIES,
   OPT_NO_GRID_INDEX, OPT_PRRT_LAT, OPT_PRRT_PIPE, OPT_PRRT_OBST_LDS, OPT_PRRT_NEXT_LDS, OPT_PRRT_ROWS, OPT_ASTAR_NO_GRID,
-  OPT_ASTAR_NO_LIST, OPT_ASTAR_PAIR, OPT_SOG_TILE, OPT_PIPE_FALLBACK, OPT_PRRT_PIPE_DRAW, OPT_PRRT_BUCKET_LDS, OPT_ROWS_STREAM, OPT_ROWS_STREAM_CAP, OPT_ROWS_STREAM_WAVES, OPT_ROWS_WG_WAVES, OPT_COUNT
+  OPT_ASTAR_NO_LIST, OPT_ASTAR_PAIR, OPT_SOG_TILE, OPT_PIPE_FALLBACK, OPT_PRRT_PIPE_DRAW, OPT_PRRT_BUCKET_LDS, OPT_ROWS_STREAM, OPT_ROWS_STREAM_CAP, OPT_ROWS_STREAM_WAVES, OPT_ROWS_WG_WAVES, OPT_ROWS_STREAM_MIRROR, OPT_COUNT
 };
 static const char* const AUVP_OPT_NAMES[OPT_COUNT] = {
   "ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
   "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
-  "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES", "ROWS_WG_WAVES"};
+  "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES", "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR"};
 
 struct auvp_handle {
   bool opt_has[OPT_COUNT] = {};
@@ -78,6 +78,7 @@ struct auvp_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr, ev_pre = nullptr;
   double last_expand_ms = 0.0, last_leaf_ms = 0.0, last_stream_ms = 0.0;
   long long last_stream_len = 0;  // numbers per episode the last pass generated ahead (0: none)
+  int last_stream_mirror = -1;    // the ring's form in the last pass's rrt_rows_stream_kernel: 1 mirrored, 0 masked (-1: another kernel ran)
   // what complete passes of RRT.exploring drew, per parameter block (the last four): the most random() numbers of one episode and
   // the largest batch seen (the length of the next batch's pre-generated stream: rrt_run_pass)
   struct Drawn { RrtParamsDev P{}; long long most = 0; int E = 0; unsigned long long used = 0; bool valid = false; };
@@ -935,6 +936,7 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   const bool use_rows = rows_ok && h->opt_flag(OPT_ROWS, E > 18 * n_cu_);
   int grid_used = grid, block_used = xw * 64, lds_used = (int)lds;
   bool stream_launched = false;
+  h->last_stream_mirror = -1;
   // latency runs (at most four episodes per CU: one episode, config 2's 1 024 replicas): two wavefronts per episode
   // (rrt_duo_kernel.h).  Option DUO = 1 / 0 forces it on (limits permitting) / off.
   const bool duo_ok = !h->lim && P.mode == 0 && !diag && nfreq <= DUO_MAX_FREQ && nfreq >= 1 && O_ <= 256 && h->max_pts <= 64;
@@ -1036,17 +1038,22 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
       int sw = (int)h->opt_num(OPT_ROWS_WG_WAVES, (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu));
       const int sw_max = (int)h->opt_num(OPT_ROWS_STREAM_WAVES, RW_WAVES);  // (the four-per-SIMD form measured 0.93 G expansions/s against 1.16: 100 B of scratch per lane at 128 registers)
       sw = sw < 1 ? 1 : (sw > sw_max ? sw_max : sw);
-      sw = sw > RW_WAVES ? RW_WAVES : sw;
-      while (sw > 1 && rrt_rows_stream_lds_plan(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), sw).total > 160 * 1024) sw--;
-      const RowsStreamLdsPlan sp = rrt_rows_stream_lds_plan(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), sw);
+      // the ring's form: its first 48 entries mirrored behind it (reads at one address per lane plus an immediate: 3 KB per
+      // episode) where that plan fits at the wave count the masked plan (2.8 KB) allows -- never a wavefront fewer for it
+      // (rrt_rows_stream_shape; option ROWS_STREAM_MIRROR = 0 / 1: the masked / the mirrored form whatever the rule says)
+      const RowsStreamShape shape = rrt_rows_stream_shape(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), sw,
+                                                          h->opt_has[OPT_ROWS_STREAM_MIRROR] ? (h->opt_val[OPT_ROWS_STREAM_MIRROR] != 0 ? 1 : 0) : -1);
+      sw = shape.waves;
+      const RowsStreamLdsPlan sp = shape.plan;
       const RowsStreamLdsPlan sp_max = sp;
+      h->last_stream_mirror = shape.mirror ? 1 : 0;
       grid_used = (E + sw * RW_ROWS - 1) / (sw * RW_ROWS); block_used = sw * 64;
       lds_used = sp.total;
       h->last_rrt_kernel = "rrt_rows_stream_kernel";
       h->last_stream_len = cap;
       le = auvpi_rrt_stream_launch(&Bs, (int)E, h->stream);
       if (le == hipSuccess) le = hipEventRecord(h->ev_pre, h->stream);
-      if (le == hipSuccess) le = auvpi_rrt_rows_stream_launch(&h->W, &PR, &Bs, (int)E, grid_used, block_used, sp_max.total, sp.total, h->stream);
+      if (le == hipSuccess) le = auvpi_rrt_rows_stream_launch(&h->W, &PR, &Bs, (int)E, grid_used, block_used, sp_max.total, sp.total, shape.mirror ? 1 : 0, h->stream);
       stream_launched = true;
     } else
     le = auvpi_rrt_rows_launch(&h->W, &PR, &B, (int)E, grid_used, block_used, rp.total, rq.total, h->stream);  // (rows_kernels.hip)
@@ -1321,6 +1328,17 @@ const char* auvp_rrt_last_kernel(auvp_handle* h) { return h ? h->last_rrt_kernel
 
 double auvp_rrt_last_stream_ms(auvp_handle* h) { return h ? h->last_stream_ms : -1.0; }
 int64_t auvp_rrt_last_stream_len(auvp_handle* h) { return h ? (int64_t)h->last_stream_len : -1; }
+int auvp_rrt_last_stream_mirror(auvp_handle* h) { return h ? h->last_stream_mirror : -1; }
+
+int auvp_rrt_rows_stream_shape(int32_t K, int32_t n_habitats, int32_t n_poly, int32_t n_bins, int32_t waves_wanted, int32_t force,
+                               int32_t* waves, int32_t* mirror, int32_t* lds_bytes) {
+  if (K < 0 || n_habitats < 0 || n_poly < 0 || n_bins < 0) return AUVP_ERR_ARG;
+  const RowsStreamShape s = rrt_rows_stream_shape(K, RW_MAX_OBST, rrt_tables_bytes(n_habitats, n_poly, n_bins), waves_wanted, force);
+  if (waves) *waves = s.waves;
+  if (mirror) *mirror = s.mirror ? 1 : 0;
+  if (lds_bytes) *lds_bytes = s.plan.total;
+  return AUVP_OK;
+}
 
 int auvp_rrt_last_leaf_stats(auvp_handle* h, int64_t* out4) {
   if (!h || !out4) return AUVP_ERR_ARG;

@@ -34,14 +34,17 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_rrt_stream_lau
 }
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_rrt_rows_stream_launch(const auvp::WorldDev* W, const auvp::RrtParamsDev* P,
                                                                                          const auvp::RrtBuffers* B, int n_episodes, int grid,
-                                                                                         int block, int lds_max, int lds, hipStream_t stream) {
+                                                                                         int block, int lds_max, int lds, int mirror, hipStream_t stream) {
   // (the kernel is a template on the largest workgroup: the four-per-SIMD form -- sixteen wavefronts, 128 registers -- measured
   // slower and is not instantiated: profiles/r6_rows_stream.md)
+  // (the kernel's requests stop at the stream's end without a test per chunk: the length is a whole number of requests)
+  if (B->stream_cap <= 0 || B->stream_cap % 64 != 0) return hipErrorInvalidValue;
   auto go = [&](auto kern) -> hipError_t {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, *W, *P, *B, n_episodes);
     return hipGetLastError();
   };
-  return go(auvp::rrt_rows_stream_kernel<auvp::RW_WAVES>);
+  // (the ring's form -- its first entries mirrored behind it or every read masked -- is the host's choice: rrt_rows_stream_shape)
+  return mirror ? go(auvp::rrt_rows_stream_kernel<auvp::RW_WAVES>) : go(auvp::rrt_rows_stream_masked_kernel<auvp::RW_WAVES>);
 }

@@ -3,8 +3,9 @@
 // n_episodes and the switch AUVP_ROWS_BODY_STREAM, #defined just before the include and #undefined after it:
 //   0  the row runs CPython's generator in its LDS block (RowRng: rows_ensure / rows_random_at / rows_advance, counted in 32-bit
 //      words) and a steer pass copies the tempered numbers it may look at into a window area of LDS;
-//   1  the row reads the numbers rrt_stream_kernel wrote ahead (RowStream: stream_ensure / stream_at / stream_advance /
-//      stream_top_up, counted in random() numbers) and the window is the ring itself.
+//   1  the row reads the numbers rrt_stream_kernel wrote ahead (RowStream: stream_ensure / stream_base + stream_read /
+//      stream_advance / stream_top_up, counted in random() numbers) and the window is the ring itself (MIRROR, a constant of
+//      the including kernel: the ring's form).
 // What differs is marked by the switch: the set-up (LDS plan, `rng`, ROWS_CONSUME), the sixteen draws of a selection round and
 // the two after the winner's, how a steer pass gets its window ready and reads it (ROWS_WIN), the stream's top-up, the epilogue.
 // Everything else is the one loop.
@@ -22,9 +23,9 @@
   const int wg_waves = (int)(blockDim.x >> 6);
   // ---- the episode's LDS block: where its random numbers come from, the running-sum scratch, the time-bin counters ----
 #if AUVP_ROWS_BODY_STREAM
-  const RowsStreamLdsPlan plan = rrt_rows_stream_lds_plan(K, RW_MAX_OBST, rrt_tables_bytes(W.n_habitats, W.n_poly, W.n_bins), wg_waves);
+  const RowsStreamLdsPlan plan = rrt_rows_stream_lds_plan(K, RW_MAX_OBST, rrt_tables_bytes(W.n_habitats, W.n_poly, W.n_bins), wg_waves, MIRROR);
   unsigned char* ebase = smem + plan.tables + (size_t)(wave * RW_ROWS + row) * plan.per_ep;
-  double* ring = reinterpret_cast<double*>(ebase);                // [RS_RING] the next random() values of the episode
+  double* ring = reinterpret_cast<double*>(ebase);                // [RS_RING (+ RS_MIRROR)] the next random() values of the episode
   double* inc = reinterpret_cast<double*>(ebase + plan.ring);     // [4][18] running sums
   uint16_t* bin_count = reinterpret_cast<uint16_t*>(ebase + plan.ring + plan.scratch);
 #else
@@ -69,7 +70,10 @@
   rng.pos = 0u; rng.front = 0u; rng.req = 0u;
   rng.cap = (uint32_t)B.stream_cap;
 #pragma unroll
-  for (int c = 0; c < RS_PEND; c++) rng.pend[c] = 0.0;
+  for (int c = 0; c < RS_PEND; c++) rng.pend[c] = rs_piece(0.0);
+#ifdef AUVP_STREAM_COUNT_SLOW
+  rng.slow = 0u;
+#endif
 #define ROWS_CONSUME(on, n) stream_advance(rng, on, (uint32_t)(n))
 #else
   RowRng rng;  // CPython's generator, its state copied in
@@ -110,12 +114,16 @@
       bool search = live;
       int fo = 0, rb = 0, cnt = 0;
       double u = 0.0;
+#if AUVP_ROWS_BODY_STREAM
+      StreamBase<MIRROR> sel;  // the round's sixteen numbers: the window at the row's position
+#endif
       for (;;) {
         // the round's sixteen draws: the next sixteen numbers of the row's stream
 #if AUVP_ROWS_BODY_STREAM
         // (a row whose stream ends before what it asks for gives up, here and below: the host redoes the batch on rrt_rows_kernel)
-        if (!stream_ensure(rng, search, 16u, rl) && search) { status = AUVP_ST_STREAM; live = false; iters_run = it; search = false; }
-        if (search) u = stream_at(rng, (uint32_t)rl);
+        if (!stream_ensure<MIRROR>(rng, search, 16u, rl) && search) { status = AUVP_ST_STREAM; live = false; iters_run = it; search = false; }
+        sel = stream_base<MIRROR>(rng, 0u, rl);
+        if (search) u = stream_read(sel, rl, rl);
 #else
         rows_ensure(rng, search, 32u, rl);
         // (they also go to the window area, free at this point: they ARE stream entries 0 .. 15 of the first pass's window
@@ -142,7 +150,7 @@
       }
       // the two draws after the winner's
 #if AUVP_ROWS_BODY_STREAM
-      const double u1 = stream_at(rng, (uint32_t)(fo + 1)), u2 = stream_at(rng, (uint32_t)(fo + 2));
+      const double u1 = stream_read(sel, fo + 1, rl), u2 = stream_read(sel, fo + 2, rl);
 #else
       wave_sync();  // (win[] was written by other lanes)
       const double u1 = win[fo + 1], u2 = win[fo + 2];
@@ -162,7 +170,7 @@
     const int n0_ = on0 ? (n_total < RW_C ? n_total : RW_C) : 0;
 #if AUVP_ROWS_BODY_STREAM
     // the window is the ring itself -- ring entry (pos + b0 + j) -- so there is nothing to build: the ring only has to reach that far
-    if (!stream_ensure(rng, on0, (uint32_t)(base + 3 * n0_), rl) && on0) { status = AUVP_ST_STREAM; live = false; iters_run = it; }
+    if (!stream_ensure<MIRROR>(rng, on0, (uint32_t)(base + 3 * n0_), rl) && on0) { status = AUVP_ST_STREAM; live = false; iters_run = it; }
 #else
     // the window is built: the numbers generated, tempered and written to win[].  A later pass's, from win[0] on:
     auto make_window = [&](bool on, int nwin, int b0) {
@@ -198,7 +206,7 @@
     // just waited for the parent's record: every older vector-memory operation -- those chunks among them -- is complete, so
     // writing them to the ring waits for nothing (at the end of the trip the same write waited for the trip's own point stores:
     // measured 45 % of the wave-cycles waiting instead of 34 %)
-    stream_top_up(rng, live, rl);
+    stream_top_up<MIRROR>(rng, live, rl);
 #endif
     const double px0 = cx, py0 = cy, clen0 = clen;
     int cnt = 0;  // appended path points of this row's steer
@@ -229,9 +237,11 @@
       // a later pass gets its window ready here (the first pass's is already: above).  ROWS_WIN(j) = window entry j of this pass
       // (a macro, not a lambda: through a lambda both kernels' code generation changed)
 #if AUVP_ROWS_BODY_STREAM
-      if (pass != 0 && !stream_ensure(rng, on, (uint32_t)nwin, rl) && on) { status = AUVP_ST_STREAM; live = false; iters_run = it; }
-      const uint32_t wb = (uint32_t)b0;
-#define ROWS_WIN(j) stream_at(rng, wb + (uint32_t)(j))
+      if (pass != 0 && !stream_ensure<MIRROR>(rng, on, (uint32_t)nwin, rl) && on) { status = AUVP_ST_STREAM; live = false; iters_run = it; }
+      // (the selection's draws, b0 of them in the first pass, are part of the window's base: the row's position itself moves
+      // when the pass is over, so a row that fails inside it reports the position it had)
+      const StreamBase<MIRROR> wb = stream_base<MIRROR>(rng, (uint32_t)b0, rl);
+#define ROWS_WIN(j) stream_read(wb, (j), rl)
 #else
       if (pass != 0) make_window(on, nwin, b0);
       const double* wp = win + (pass == 0 ? base : 0);
@@ -494,8 +504,8 @@
 #if AUVP_ROWS_BODY_STREAM
   const unsigned long long drawn = 2ull * rng.pos;  // (two per random())
   // a stream that ends exactly here has no next number: reported like any other end
-  if (!stream_ensure(rng, valid && status == 0, 1u, rl) && valid && status == 0) status = AUVP_ST_STREAM;
-  const double after = status == AUVP_ST_STREAM ? 0.0 : stream_at(rng, 0u);
+  if (!stream_ensure<MIRROR>(rng, valid && status == 0, 1u, rl) && valid && status == 0) status = AUVP_ST_STREAM;
+  const double after = status == AUVP_ST_STREAM ? 0.0 : stream_read(stream_base<MIRROR>(rng, 0u, rl), rl, rl);
 #else
   const unsigned long long drawn = rng.drawn;
   rows_ensure(rng, valid, 2u, rl);
@@ -514,6 +524,9 @@
       s.best_cost[0] = __builtin_inf(); s.best_cost[1] = 0.0; s.best_cost[2] = 0.0; s.best_cost[3] = 0.0;
       s.best_length = 0.0;
       s.rng_after = after; s.leaf_elems = 0; s.n_draw32 = drawn; s.nn_scanned = 0ull;
+#if AUVP_ROWS_BODY_STREAM && defined(AUVP_STREAM_COUNT_SLOW)
+      s.nn_scanned = rng.slow;  // EXPERIMENT ONLY (tools/stream_slow_probe.py): the field is unused in time-bin mode
+#endif
     }
   }
 #undef ROWS_CONSUME

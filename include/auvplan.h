@@ -404,6 +404,14 @@ int auvp_rrt_last_launch_parts(auvp_handle* h, double* expand_ms, double* leaf_m
 double auvp_rrt_last_stream_ms(auvp_handle* h);
 /* ... and how many random() numbers per episode that launch wrote (8 bytes each; 0: none) */
 int64_t auvp_rrt_last_stream_len(auvp_handle* h);
+/* ... and the form of the LDS ring rrt_rows_stream_kernel read them through: 1 its first 48 entries mirrored behind it, 0 every
+ * read masked (-1: the last auvp_rrt_run launched another expansion kernel) */
+int auvp_rrt_last_stream_mirror(auvp_handle* h);
+/* The launch the host would choose for rrt_rows_stream_kernel (no device needed): K time bins, a world with these table sizes,
+ * waves_wanted wavefronts per workgroup (1 .. 12), force < 0 the host's rule / 0 the masked / 1 the mirrored ring.  Out: the
+ * wavefronts per workgroup, the ring's form, the workgroup's LDS bytes.  The rule never gives up a wavefront for the mirror. */
+int auvp_rrt_rows_stream_shape(int32_t K, int32_t n_habitats, int32_t n_poly, int32_t n_bins, int32_t waves_wanted, int32_t force,
+                               int32_t* waves, int32_t* mirror, int32_t* lds_bytes);
 /* name of the expansion kernel the last auvp_rrt_run launched: "rrt_rows_kernel" (four episodes per wavefront: batches of
  * more than 18 episodes per CU; "rrt_rows_stream_kernel": the same with the random numbers generated ahead by
  * rrt_stream_kernel), "rrt_explore_kernel" (one), "rrt_duo_kernel" (two wavefronts per episode: batches of at
