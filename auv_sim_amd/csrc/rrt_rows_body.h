@@ -100,7 +100,17 @@
   wave_sync();
   int n_nodes = 1, n_points = 0, status = 0, n_cand = 0, iters_run = 0;
   // lane rl keeps the bounding box of obstacle slot rl: one compare round tells which slots a steer can touch
-  const double4 sbox = reinterpret_cast<const double4*>(W.os_box)[rl];
+  double4 sbox_ld = reinterpret_cast<const double4*>(W.os_box)[rl];
+  // (the empty statement makes the four components arrive HERE: used first inside the loop, the load stayed pending over the
+  // loop's header and its first use in the cull drained the vector-memory counter -- the trip's own point stores with it --
+  // in every trip: profiles/rows_trip_waits.md.  No instruction per trip.)
+  asm volatile("" : "+v"(sbox_ld.x), "+v"(sbox_ld.y), "+v"(sbox_ld.z), "+v"(sbox_ld.w));
+  const double4 sbox = sbox_ld;
+  // the obstacles' thresholds are read through the scalar data path (constant address space: the table is written by the host
+  // before the launch and by nobody during it), so that no vector-memory load -- and no wait on the one in-order counter the
+  // point stores share -- is left in the collision test
+  typedef const __attribute__((address_space(4))) double* rows_ost_ptr;
+  const rows_ost_ptr ost_s = (rows_ost_ptr)W.os_t;
   const int nv_poly = W.n_poly;
 
   for (int it = 0; it < P.max_iter; it++) {
@@ -202,10 +212,11 @@
       clen = nodeF[(size_t)par * 8 + 4];
     }
 #if AUVP_ROWS_BODY_STREAM
-    // once per trip: the chunks requested a trip ago go into the ring, the next ones are requested.  Here, because the kernel has
-    // just waited for the parent's record: every older vector-memory operation -- those chunks among them -- is complete, so
-    // writing them to the ring waits for nothing (at the end of the trip the same write waited for the trip's own point stores:
-    // measured 45 % of the wave-cycles waiting instead of 34 %)
+    // once per trip: the chunks requested a trip ago go into the ring, the next ones are requested.  Those chunks arrived with
+    // the parent's record of the trip before (the first pass's wait for it covers them: they are older), so the write waits for
+    // nothing -- as long as every way through a trip passes that wait, which is why the first pass is not skipped (below) and
+    // why stream_ensure's slow path settles what it requested.  (At the end of the trip the same write waited for the trip's
+    // own point stores: measured 45 % of the wave-cycles waiting instead of 34 %)
     stream_top_up<MIRROR>(rng, live, rl);
 #endif
     const double px0 = cx, py0 = cy, clen0 = clen;
@@ -218,7 +229,12 @@
     for (int pass = 0; pass < 2; pass++) {
       const int c0 = pass * RW_C;
       const bool on = live && c0 < n_total;  // rows with sub-arcs left
-      if (!wave_any(on)) break;
+      // (the first pass runs whatever the rows ask for: with no row `on` -- every live row drew zero sub-arcs, rare -- it is a
+      // pass of zeros that changes nothing, and the parent's record then has ONE place where it is first used.  With a way
+      // round the pass the record stayed "on its way" for the compiler on that way, and the ring write above and the trip's
+      // tail drained the vector-memory counter -- the point stores with it -- for registers nobody was waiting for:
+      // profiles/rows_trip_waits.md)
+      if (pass != 0 && !wave_any(on)) break;
       const int n = on ? ((n_total - c0) < RW_C ? (n_total - c0) : RW_C) : 0;
       const int nwin = 3 * n;
 #ifdef AUVP_ROWS_PAD
@@ -412,7 +428,11 @@
         sm &= sm - 1u;
         const int oi = j0 + rl;
         const double oxj = olx[oi], oyj = oly[oi], orj = (double)olr[oi];
-        const double otj = W.os_t[oi];  // this lane's obstacle of the slot: one coalesced read, handed out below
+#ifdef AUVP_ROWS_OST_LDS
+        // EXPERIMENT ONLY (profiles/rows_trip_waits.md; never defined in the product build): a stand-in threshold from the LDS
+        // tile -- NOT the obstacle's, the results are wrong -- to price a collision test without any vector-memory load
+        const double otj = orj * orj;
+#endif
         const bool cand = hs_ && (TIGHT ? !(auvp_fabs(oxj - tcx) > thx + orj || auvp_fabs(oyj - tcy) > thy + orj)
                                         : !(auvp_fabs(oxj - px0) > hx + orj || auvp_fabs(oyj - py0) > hx + orj));
         uint32_t cm = row_ballot(cand, rowbase);
@@ -421,7 +441,24 @@
           const bool has = cm != 0u;
           const int cl = has ? (__ffs((int)cm) - 1) : 0;
           cm &= cm - 1u;
-          const double ox = row_read_f64(oxj, rowbase + cl), oy = row_read_f64(oyj, rowbase + cl), ot = row_read_f64(otj, rowbase + cl);
+          const double ox = row_read_f64(oxj, rowbase + cl), oy = row_read_f64(oyj, rowbase + cl);
+#ifdef AUVP_ROWS_OST_LDS
+          const double ot = row_read_f64(otj, rowbase + cl);
+#else
+          // the threshold of each row's candidate, obstacle j0 + cl (row-uniform, 0 .. 255 also for a row without one): four
+          // scalar loads, each row keeps its own
+          const int oc = j0 + cl;
+          const unsigned long long hasm = __builtin_amdgcn_uicmp((unsigned)has, 0u, 33 /* != */);
+          double ot = 0.0;
+          int rowv = row;
+          asm volatile("" : "+v"(rowv));
+#pragma unroll
+          for (int r = 0; r < RW_ROWS; r++)
+            if (hasm & (1ull << (16 * r))) {
+              const double t = ost_s[__builtin_amdgcn_readlane(oc, 16 * r)];
+              ot = rowv == r ? t : ot;
+            }
+#endif
 #pragma unroll
           for (int q = 0; q < 2; q++) {
             const double ddx = ptx[q] - ox, ddy = pty[q] - oy;

@@ -117,6 +117,11 @@ __device__ __forceinline__ void stream_request(RowStream& r, bool on, int rl) {
       r.pend[c] = __builtin_nontemporal_load(reinterpret_cast<const rs_piece*>(r.src + r.req + (uint32_t)(RS_CHUNK * c) + (uint32_t)(RS_PIECE * rl)));
   r.req += (uint32_t)RS_CHUNK * n;
 }
+// the chunks on their way have arrived from here on, as far as the compiler's count of pending loads goes (no instruction)
+__device__ __forceinline__ void stream_settle(RowStream& r) {
+#pragma unroll
+  for (int c = 0; c < RS_PEND; c++) asm volatile("" : "+v"(r.pend[c]));
+}
 // once per trip: what was requested a trip ago is written, the next chunks are requested
 template <bool MIRROR>
 __device__ __forceinline__ void stream_top_up(RowStream& r, bool on, int rl) {
@@ -141,6 +146,7 @@ __device__ __forceinline__ bool stream_ensure(RowStream& r, bool want, uint32_t 
     stream_commit<MIRROR>(r, rl);
     stream_request(r, go && ok, rl);
     stream_commit<MIRROR>(r, rl);
+    stream_settle(r);  // (without it the chunks count as on their way after the loop, and their next use drains the counter)
     wave_sync();
     if (!wave_any(go && ok && r.front - r.pos < need_w)) break;
   }
