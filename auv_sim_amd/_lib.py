@@ -194,6 +194,82 @@ def rows_stream_shape(K, n_habitats, n_poly, n_bins, waves_wanted=12, force=-1):
     return w.value, bool(m.value), l.value
 
 
+class _RrtLaunchQuery(C.Structure):
+    _fields_ = [("n_episodes", C.c_int32), ("n_cu", C.c_int32), ("mode", C.c_int32), ("max_iter", C.c_int32),
+                ("n_time_bins", C.c_int32), ("flags", C.c_int32), ("freq", C.c_double), ("dist_to_end", C.c_double),
+                ("max_pts", C.c_int32), ("n_obstacles", C.c_int32), ("n_habitats", C.c_int32), ("n_poly", C.c_int32),
+                ("n_bins", C.c_int32), ("obst_area", C.c_double), ("per_episode_limits", C.c_int32), ("one_wave_only", C.c_int32),
+                ("no_stream", C.c_int32), ("seen_E", C.c_int32), ("seen_most", C.c_int64), ("n_options", C.c_int32),
+                ("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
+
+
+class _RrtLaunchChoice(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "J", "quad", "grid", "block", "lds", "lds_max", "kflags", "stream_waves",
+                                         "mirror", "_pad")] + [("stream_len", C.c_int64), ("lds_need", C.c_int64), ("name", C.c_char_p)]
+
+
+class _PrrtLaunchQuery(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_episodes", "n_cu", "n_obstacles", "max_pts", "cap_nodes", "n_buckets", "max_step", "flags")] + \
+               [("freq", C.c_double)] + [(n, C.c_int32) for n in ("step_mode", "waits", "one_wave_only", "rows", "n_options", "_pad")] + \
+               [("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
+
+
+class _PrrtLaunchChoice(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "lat", "rows", "pipe", "draw_wave", "next_lds", "bk_lds", "obst_lds", "eps_wg",
+                                         "grid", "block", "lds", "J")] + [("lds_need", C.c_int64), ("name", C.c_char_p)]
+
+
+RRT_KINDS = ("explore", "explore_lim", "duo", "trio", "rows", "rows_stream")
+PRRT_KINDS = ("one", "pipe", "rows")
+KFLAG_TIGHT_CULL, KFLAG_NN_EXACT = 1024, 2048
+
+
+def _ask_launch(fn, query, choice, options, kinds):
+    opts = sorted((options or {}).items())
+    names = (C.c_char_p * max(len(opts), 1))(*[k.encode() for k, _ in opts])
+    values = (C.c_int64 * max(len(opts), 1))(*[int(v) for _, v in opts])
+    query.n_options, query.option_names, query.option_values = len(opts), names, values
+    rc = getattr(load(), fn)(C.byref(query), C.byref(choice))
+    if rc != 0:
+        raise AuvpError(rc, fn + ": bad argument or unknown option")
+    out = {n: getattr(choice, n) for n, _ in choice._fields_ if n != "_pad"}
+    out["name"] = (choice.name or b"").decode()
+    out["kind"] = kinds[choice.kind]
+    return out
+
+
+def rrt_choose_launch(E, n_cu=256, mode="timebin", max_iter=10000, K=100, flags=0, freq=30.0, dist_to_end=2.0, max_pts=None,
+                      O=0, H=0, V=0, T=0, obst_area=0.0, lim=False, one_wave_only=False, no_stream=False, seen_most=0, seen_E=0,
+                      options=None):
+    """the expansion launch the host would choose for this RRT.exploring batch (auvp_rrt_choose_launch; no GPU needed): a dict
+    of the plan -- kind (one of RRT_KINDS), name, J, quad, grid, block, lds, lds_max, kflags, stream_len, stream_waves, mirror,
+    status (0, or -1 with lds_need: the LDS plan does not fit).  K: time bins (ceil(max_traj_time / bin_interval) in time-bin
+    mode); O, H, V, T: the world's obstacles, habitats, boundary vertices, time bins; options: {name: value} of the options that
+    are set; seen_most / seen_E: what earlier batches with the same parameters drew (0: nothing seen)"""
+    import math
+    q = _RrtLaunchQuery(n_episodes=int(E), n_cu=int(n_cu), mode=MODES.get(mode, mode), max_iter=int(max_iter),
+                        n_time_bins=int(K), flags=int(flags), freq=float(freq), dist_to_end=float(dist_to_end),
+                        max_pts=int(math.floor(freq)) + 2 if max_pts is None else int(max_pts), n_obstacles=int(O), n_habitats=int(H),
+                        n_poly=int(V), n_bins=int(T), obst_area=float(obst_area), per_episode_limits=int(bool(lim)),
+                        one_wave_only=int(bool(one_wave_only)), no_stream=int(bool(no_stream)), seen_E=int(seen_E), seen_most=int(seen_most))
+    return _ask_launch("auvp_rrt_choose_launch", q, _RrtLaunchChoice(), options, RRT_KINDS)
+
+
+def prrt_choose_launch(E, n_cu=256, O=0, freq=10.0, max_step=300, n_buckets=0, flags=0, max_pts=None, cap_nodes=None, step_mode=0,
+                       waits=True, one_wave_only=False, rows=None, options=None):
+    """the launch the host would choose for this Planner_RRT batch (auvp_prrt_choose_launch; no GPU needed): a dict of the plan --
+    kind (one of PRRT_KINDS), name, lat, rows, pipe, draw_wave, next_lds, bk_lds, obst_lds, eps_wg, grid, block, lds, J, status.
+    step_mode 0 / waits True: plan(); step_mode 1: step(); waits False: a step of the device-resident loop.  rows: None decides the
+    four-episode choice as creating the batch does, True / False is the batch's frozen choice"""
+    import math
+    q = _PrrtLaunchQuery(n_episodes=int(E), n_cu=int(n_cu), n_obstacles=int(O),
+                         max_pts=int(math.floor(freq)) + 3 if max_pts is None else int(max_pts),
+                         cap_nodes=int(max_step) + 1 if cap_nodes is None else int(cap_nodes), n_buckets=int(n_buckets),
+                         max_step=int(max_step), flags=int(flags), freq=float(freq), step_mode=int(step_mode), waits=int(bool(waits)),
+                         one_wave_only=int(bool(one_wave_only)), rows=-1 if rows is None else int(bool(rows)))
+    return _ask_launch("auvp_prrt_choose_launch", q, _PrrtLaunchChoice(), options, PRRT_KINDS)
+
+
 class Context:
     """One planner context = one HIP device + stream + device-resident world and tree storage."""
 

@@ -220,9 +220,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
       // latency batches on a product grid: a second wavefront per instance (astar_kernel.h, PAIR); option ASTAR_PAIR = 0 / 1
       // forces the choice.  Not with a visited array the caller carries over (KEEP_VISITED): a batch that had to be repeated on
       // the one-wavefront kernel (pipeline fallback, below) could not get it back.
-      int n_cu = 256;
-      (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-      pair = S.W.g_ncol > 0 && !(flags & AUVP_FLAG_KEEP_VISITED) && h->opt_flag(OPT_ASTAR_PAIR, E <= (size_t)8 * (size_t)(n_cu > 0 ? n_cu : 256));
+      pair = S.W.g_ncol > 0 && !(flags & AUVP_FLAG_KEEP_VISITED) && h->opt_flag(OPT_ASTAR_PAIR, E <= (size_t)8 * (size_t)h->n_cu);
       if (pair) hipLaunchKernelGGL((auvp::astar_kernel<3, true>), dim3(grid), dim3(auvp::ASTAR_WAVES * 128), 0, h->stream, S.W, P, B, (int)E);
       else hipLaunchKernelGGL(auvp::astar_kernel<3>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E);
       break;

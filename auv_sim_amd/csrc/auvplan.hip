@@ -22,6 +22,11 @@
 #include "rrt_rows_stream_kernel.h"  // (the LDS plan; the kernel itself is launched from rows_kernels.hip)
 #include "rrt_duo_kernel.h"
 #include "rrt_trio_kernel.h"
+#include "planner_rrt_kernel.h"
+#include "planner_rows_kernel.h"
+#include "planner_goal_arc.h"
+#include "planner_pipe_kernel.h"
+#include "launch_plan.h"  // (behind every kernel header whose LDS plan and limits the choice reads)
 
 using namespace auvp;
 
@@ -53,27 +58,13 @@ struct DevBuf {
 
 }  // namespace
 
-// Tuning / diagnostic options of a handle (auvp_set_option, include/auvplan.h).  Every kernel choice the host makes has a
-// measured default ("auto": the option is unset); an option forces it.  The environment variable AUVP_<NAME> gives an
-// option its initial value ONCE, when the handle is created -- no launch path reads the environment.
-enum AuvpOpt {
-  OPT_ROWS, OPT_DUO, OPT_TRIO, OPT_QUAD, OPT_TIGHT_CULL, OPT_NN_EXACT, OPT_LEAF_SWEEP_ALL, OPT_NO_HABITAT_GRID, OPT_RG_MAX_ENTRIES,
-  OPT_NO_GRID_INDEX, OPT_PRRT_LAT, OPT_PRRT_PIPE, OPT_PRRT_OBST_LDS, OPT_PRRT_NEXT_LDS, OPT_PRRT_ROWS, OPT_ASTAR_NO_GRID,
-  OPT_ASTAR_NO_LIST, OPT_ASTAR_PAIR, OPT_SOG_TILE, OPT_PIPE_FALLBACK, OPT_PRRT_PIPE_DRAW, OPT_PRRT_BUCKET_LDS, OPT_ROWS_STREAM, OPT_ROWS_STREAM_CAP, OPT_ROWS_STREAM_WAVES, OPT_ROWS_WG_WAVES, OPT_ROWS_STREAM_MIRROR, OPT_COUNT
-};
-static const char* const AUVP_OPT_NAMES[OPT_COUNT] = {
-  "ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
-  "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
-  "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES", "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR"};
-
 struct auvp_handle {
-  bool opt_has[OPT_COUNT] = {};
-  long long opt_val[OPT_COUNT] = {};
-  // option K as a yes / no choice: its value when set, `dflt` (the measured heuristic) otherwise
-  bool opt_flag(int k, bool dflt) const { return opt_has[k] ? opt_val[k] != 0 : dflt; }
-  bool opt_on(int k) const { return opt_has[k] && opt_val[k] != 0; }
-  long long opt_num(int k, long long dflt) const { return opt_has[k] ? opt_val[k] : dflt; }
+  OptionView opt;  // the options (launch_plan.h: the list, the accessors)
+  bool opt_flag(int k, bool dflt) const { return opt.opt_flag(k, dflt); }
+  bool opt_on(int k) const { return opt.opt_on(k); }
+  long long opt_num(int k, long long dflt) const { return opt.opt_num(k, dflt); }
   int device = 0;
+  int n_cu = 256;  // compute units of the device (256 where the query fails): read once, by auvp_create
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr, ev_pre = nullptr;
   double last_expand_ms = 0.0, last_leaf_ms = 0.0, last_stream_ms = 0.0;
@@ -267,8 +258,9 @@ int auvp_create(int device, auvp_handle** out) {
   // options: initial values from AUVP_<NAME>, read here and nowhere else
   for (int k = 0; k < OPT_COUNT; k++) {
     const std::string name = std::string("AUVP_") + AUVP_OPT_NAMES[k];
-    if (const char* e = getenv(name.c_str())) { h->opt_has[k] = true; h->opt_val[k] = atoll(e); }
+    if (const char* e = getenv(name.c_str())) { h->opt.opt_has[k] = true; h->opt.opt_val[k] = atoll(e); }
   }
+  if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
   if (hipHostMalloc(reinterpret_cast<void**>(&h->pipe_fail_host), 64, hipHostMallocMapped) == hipSuccess) {
     h->pipe_fail_host[0] = 0;
     if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pipe_fail_dev), h->pipe_fail_host, 0) != hipSuccess) h->pipe_fail_dev = nullptr;
@@ -291,27 +283,27 @@ int auvp_create(int device, auvp_handle** out) {
 
 int auvp_set_option(auvp_handle* h, const char* name, int64_t value) {
   if (!h || !name) return AUVP_ERR_ARG;
-  for (int k = 0; k < OPT_COUNT; k++)
-    if (!strcmp(name, AUVP_OPT_NAMES[k])) { h->opt_has[k] = true; h->opt_val[k] = value; return AUVP_OK; }
-  return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  const int k = auvp_option_index(name);
+  if (k < 0) return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  h->opt.opt_has[k] = true; h->opt.opt_val[k] = value;
+  return AUVP_OK;
 }
 
 int auvp_unset_option(auvp_handle* h, const char* name) {
   if (!h || !name) return AUVP_ERR_ARG;
-  for (int k = 0; k < OPT_COUNT; k++)
-    if (!strcmp(name, AUVP_OPT_NAMES[k])) { h->opt_has[k] = false; h->opt_val[k] = 0; return AUVP_OK; }
-  return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  const int k = auvp_option_index(name);
+  if (k < 0) return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  h->opt.opt_has[k] = false; h->opt.opt_val[k] = 0;
+  return AUVP_OK;
 }
 
 int auvp_get_option(auvp_handle* h, const char* name, int32_t* is_set, int64_t* value) {
   if (!h || !name) return AUVP_ERR_ARG;
-  for (int k = 0; k < OPT_COUNT; k++)
-    if (!strcmp(name, AUVP_OPT_NAMES[k])) {
-      if (is_set) *is_set = h->opt_has[k] ? 1 : 0;
-      if (value) *value = h->opt_val[k];
-      return AUVP_OK;
-    }
-  return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  const int k = auvp_option_index(name);
+  if (k < 0) return fail(h, AUVP_ERR_ARG, "unknown option %s", name);
+  if (is_set) *is_set = h->opt.opt_has[k] ? 1 : 0;
+  if (value) *value = h->opt.opt_val[k];
+  return AUVP_OK;
 }
 
 int auvp_pipeline_fallbacks(auvp_handle* h, int32_t* last, int64_t* total) {
@@ -518,14 +510,10 @@ int auvp_world_set(auvp_handle* h, const double* obstacles, int32_t O, const dou
     const int NS = 256;
     std::vector<double> sx(NS, 0.0), sy(NS, 0.0), st(NS, -1.0), box(16 * 4);
     std::vector<float> sr(NS, -INFINITY);
-    {
-      double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
-      for (int i = 0; i < O; i++) { x0 = std::min(x0, ox[i]); x1 = std::max(x1, ox[i]); y0 = std::min(y0, oy[i]); y1 = std::max(y1, oy[i]); }
-      h->obst_area = (O > 1 && std::isfinite((x1 - x0) * (y1 - y0))) ? (x1 - x0) * (y1 - y0) : 0.0;
-    }
+    double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;  // bounding box of the obstacle centres
+    for (int i = 0; i < O; i++) { x0 = std::min(x0, ox[i]); x1 = std::max(x1, ox[i]); y0 = std::min(y0, oy[i]); y1 = std::max(y1, oy[i]); }
+    h->obst_area = (O > 1 && std::isfinite((x1 - x0) * (y1 - y0))) ? (x1 - x0) * (y1 - y0) : 0.0;
     if (O <= NS) {
-      double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
-      for (int i = 0; i < O; i++) { x0 = std::min(x0, ox[i]); x1 = std::max(x1, ox[i]); y0 = std::min(y0, oy[i]); y1 = std::max(y1, oy[i]); }
       auto spread = [](uint32_t v) { uint64_t x = v & 0xffff; x = (x | (x << 8)) & 0x00ff00ff; x = (x | (x << 4)) & 0x0f0f0f0f;
                                      x = (x | (x << 2)) & 0x33333333; x = (x | (x << 1)) & 0x55555555; return x; };
       std::vector<std::pair<uint64_t, int>> key(O);
@@ -742,12 +730,9 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
   // the pre-generated random stream of earlier batches (tens of GB, rrt_run_pass) stays with the handle while the batches are of
   // its kind -- a caller alternating between worlds does not pay a hipMalloc per call -- and goes back before a batch of
   // another kind reserves its own buffers
-  if (h->d_stream.p) {
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-    if (lim || !(P.mode == 0 && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true) && h->opt_flag(OPT_ROWS, E > 18 * (n_cu > 0 ? n_cu : 256))))
-      h->d_stream.release();
-  }
+  if (h->d_stream.p && (lim || !(P.mode == 0 && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true) &&
+                                 h->opt_flag(OPT_ROWS, rrt_rows_by_size(E, h->n_cu)))))
+    h->d_stream.release();
   RrtBuffers& B = h->B;
   B.cap_nodes = p->max_iter + 1;
   // Path-point budget.  A steer appends at most n = floor(uniform(0, freq)) points (:258-262) and only an accepted one
@@ -848,16 +833,8 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
 
 }  // extern "C"
 
-// one pass over the prepared batch: the expansion launch + the leaf pass.  one_wave_only: never a speculative pipeline
-// The pre-generated random stream of a batch (rrt_stream_kernel.h): its length in numbers per episode -- from what the previous
-// batches with the same parameters drew (`seen`), else 46.5 per iteration + 4 096 -- and its buffer.
-static long long rrt_stream_len(const auvp_handle* h, const auvp_handle::Drawn* seen) {
-  const long long guess = seen ? seen->most + seen->most * 3 / 100 + 1024 : (long long)(46.5 * (double)h->P.max_iter) + 4096;
-  long long cap = h->opt_num(OPT_ROWS_STREAM_CAP, guess);
-  cap = cap < 64 ? 64 : cap;
-  return (cap + 63) / 64 * 64;
-}
-// 1: the buffer holds `bytes`; 0: it does not fit the free memory beside a 4 GB margin (or the allocation failed).  A buffer that
+// 1: the buffer of the pre-generated random stream (rrt_stream_kernel.h) holds `bytes`; 0: it does not fit the free memory beside
+// a 4 GB margin (or the allocation failed).  A buffer that
 // has to grow is taken 6 % larger than asked for: the length follows the busiest episode seen so far, which creeps up by a few
 // parts in a thousand from batch to batch, and every re-allocation of tens of GB is a second or two of hipFree + hipMalloc.
 // *grew: an allocation happened (the caller re-records its start event: nothing has been launched yet)
@@ -877,266 +854,102 @@ static int rrt_stream_reserve(auvp_handle* h, size_t bytes, bool* grew = nullptr
   return 1;
 }
 
-// no_stream: the random numbers are generated inside the expansion kernel whatever option ROWS_STREAM says (the stream fallback)
-static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = false) {
-  const RrtParamsDev& P = h->P;
+// one kernel launch at the plan's shape
+template <class Kern, class... Args>
+static hipError_t launch_kernel(Kern kern, int grid, int block, int lds, hipStream_t stream, const Args&... args) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, args...);
+  return hipGetLastError();
+}
+
+// the expansion launch the plan names.  PR: the parameters with the plan's kernel flags
+static hipError_t rrt_launch_expansion(auvp_handle* h, const RrtLaunchPlan& plan, const RrtParamsDev& PR) {
   const RrtBuffers& B = h->B;
-  const int E = h->E;
-  const int nfreq = (int)std::floor(P.freq);
-  const int O_ = h->W.n_obstacles;
-  // Where the obstacles are dense the cull of a steer uses the tight box of its path points instead of the square of
-  // its total movement (fewer exact tests for ~100 extra instructions): decided here from the expected number of
-  // obstacles inside a typical reach square, 4 (freq dist_to_end / 4)^2 O / (area of the obstacles' bounding box).
-  RrtParamsDev PR = P;
-  {
-    const double reach = 0.25 * P.freq * P.dist_to_end;
-    const double lam = h->obst_area > 0.0 ? 4.0 * reach * reach * (double)O_ / h->obst_area : (O_ > 0 ? 1e9 : 0.0);
-    if (h->opt_flag(OPT_TIGHT_CULL, lam > 0.5)) PR.flags |= AUVP_KFLAG_TIGHT_CULL;
-    if (h->opt_on(OPT_NN_EXACT)) PR.flags |= AUVP_KFLAG_NN_EXACT;
-  }
-  const int jslots = (O_ <= 64 ? 1 : (O_ <= 128 ? 2 : (O_ <= 256 ? 4 : (O_ <= 512 ? 8 : 16)))) * 64;
-  int n_cu_ = 256;
-  (void)hipDeviceGetAttribute(&n_cu_, hipDeviceAttributeMultiprocessorCount, h->device);
-  if (n_cu_ <= 0) n_cu_ = 256;
-  const bool diag = (P.flags & (AUVP_FLAG_ITER_LOG | AUVP_FLAG_LEAF_LOG | AUVP_FLAG_PHASE_CLOCKS)) != 0;
-  // Small batches (at most eight episodes per CU: config 2's 1 024 replicas) get workgroups of fewer waves, so that every CU
-  // holds one (1 024 episodes: 256 workgroups of four waves = one wave per SIMD, instead of 128 CUs with two per SIMD:
-  // 208 -> 229 M expansions/s).  A latency instantiation on top of that -- 124 VGPRs without the 80-register cap, the steer's
-  // running sums as 32 unrolled steps with all reads up front -- was bit-identical and SLOWER (4.2 -> 5.7 us per expansion:
-  // the loops only run n / 2 ~ 7 trips) and is not kept.
-  const bool small_batch = E <= 8 * n_cu_;
-  int xw = RRT_X_WAVES;
-  if (small_batch) { xw = (E + n_cu_ - 1) / n_cu_; xw = xw < 1 ? 1 : (xw > RRT_X_WAVES ? RRT_X_WAVES : xw); }
-  const size_t lds = (size_t)rrt_lds_plan(P.K, h->max_pts, nfreq, jslots,
-                                          rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), xw).total;
-  if (lds > 160 * 1024) return fail(h, AUVP_ERR_ARG, "LDS need %zu B > 160 KiB (K=%d, freq=%d)", lds, P.K, nfreq);
-  const int grid = (E + xw - 1) / xw;
-  const int O = h->W.n_obstacles;
-  auto launch = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(xw * 64), lds, h->stream, h->W, PR, B, (int)E, h->max_pts);
-    return hipGetLastError();
-  };
-  if (B.leaf_stats) HIPCHK(h, hipMemsetAsync(B.leaf_stats, 0, 8 * sizeof(unsigned long long), h->stream));  // (before the timed region)
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  hipError_t le = hipSuccess;
-  // four episodes per wavefront (rrt_rows_kernel.h) where its limits allow; one episode per wavefront otherwise
-  const RowsLdsPlan rp = rrt_rows_lds_plan(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins));
-  const bool iter_log = (P.flags & (AUVP_FLAG_ITER_LOG | AUVP_FLAG_PHASE_CLOCKS)) != 0;
-  // ... and where it pays: a batch the one-episode kernel can keep resident in one go (6 waves per SIMD = 24 episodes per
-  // CU) runs faster there -- the rows kernel would leave the SIMDs with one or two waves.  Measured on MI355X, M
-  // expansions/s one-episode vs rows: 4 096 episodes 616 vs 507, 6 144 episodes 704 vs 645, 8 192 episodes 699 vs 849,
-  // 10 240 episodes 737 vs 877.  End of round 6 (the rows kernel has lost a quarter of its instructions since), same batches:
-  // 4 096 episodes 631 vs 606, 5 120: 609 vs 647, 6 144: 727 vs 773, 8 192: 715 vs 1 014 -- the crossover is between 16 and 20
-  // episodes per CU now: rows above 18 (tools/batch_size_probe.py).  Option ROWS = 1 / 0 forces it on (limits permitting) / off.
-  // (a batch with per-episode limits runs rrt_explore_lim_kernel, whatever the options say)
-  const bool rows_ok = !h->lim && P.mode == 0 && !iter_log && nfreq <= RW_MAX_FREQ && O_ <= RW_MAX_OBST && P.max_iter < 65534 &&
-                       rp.total <= 160 * 1024;
-  const bool use_rows = rows_ok && h->opt_flag(OPT_ROWS, E > 18 * n_cu_);
-  int grid_used = grid, block_used = xw * 64, lds_used = (int)lds;
-  bool stream_launched = false;
-  h->last_stream_mirror = -1;
-  // latency runs (at most four episodes per CU: one episode, config 2's 1 024 replicas): two wavefronts per episode
-  // (rrt_duo_kernel.h).  Option DUO = 1 / 0 forces it on (limits permitting) / off.
-  const bool duo_ok = !h->lim && P.mode == 0 && !diag && nfreq <= DUO_MAX_FREQ && nfreq >= 1 && O_ <= 256 && h->max_pts <= 64;
-  // Measured (tools/duo_probe.py, M expansions/s one vs two wavefronts per episode): 1 episode 0.25 vs 0.32, 256: 62 vs 80,
-  // 1 024: 227 vs 271 (config 2's replicas, 64 obstacles: 241 vs 283), 2 048: 409 vs 435, 4 096: 621 vs 485
-  const bool use_duo = duo_ok && !use_rows && !one_wave_only && h->opt_flag(OPT_DUO, E <= 8 * n_cu_);
-  // ... and three (rrt_trio_kernel.h: stream, geometry, tree -- a pipeline over the iterations) for at most four episodes per
-  // CU.  Measured (tools/duo_probe.py, M expansions/s, one / two / three wavefronts per episode): 1 episode 0.25 / 0.32 / 0.40,
-  // 256: 61 / 80 / 95, 1 024: 226 / 271 / 303 (config 2's replicas: 239 / 282 / 309), 2 048: 406 / 434 / 304.
-  // Option TRIO = 1 / 0 forces it on (limits permitting) / off; an explicit DUO = 1 takes precedence.
-  const bool use_trio = duo_ok && !use_rows && !one_wave_only && h->opt_flag(OPT_TRIO, E <= TRIO_EP * n_cu_ && !h->opt_on(OPT_DUO));
-  h->last_rrt_kernel = use_rows ? "rrt_rows_kernel" : (use_trio ? "rrt_trio_kernel" : (use_duo ? "rrt_duo_kernel" : "rrt_explore_kernel"));
-  if (h->lim) h->last_rrt_kernel = "rrt_explore_lim_kernel";
-  h->last_stream_ms = 0.0;
-  h->last_stream_len = 0;
-  if (use_trio) {
-    int eps_wg = (E + n_cu_ - 1) / n_cu_;
-    eps_wg = eps_wg < 1 ? 1 : (eps_wg > TRIO_EP ? TRIO_EP : eps_wg);
-    const int jd = O_ <= 64 ? 1 : (O_ <= 128 ? 2 : 4);
-    const int dl = trio_lds_bytes(P.K, jd * 64, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), eps_wg);
-    if (dl > 160 * 1024) return fail(h, AUVP_ERR_ARG, "LDS need %d B > 160 KiB (K=%d)", dl, P.K);
-    // the parent lookup as a fourth wavefront per episode (rrt_trio_kernel<J, 4>) where every episode has a CU to itself: one
-    // episode 2.52 -> 2.49 us per expansion, 256 episodes 95 -> 100 M/s (1 024: 303 -> 262 M/s, so not there).  Option QUAD
-    const bool quad = h->opt_flag(OPT_QUAD, E <= n_cu_);
-    grid_used = (E + eps_wg - 1) / eps_wg; block_used = eps_wg * (quad ? 256 : 192); lds_used = dl;
-    if (quad) h->last_rrt_kernel = "rrt_trio_kernel<4 wavefronts>";
-    auto launch_trio = [&](auto kern) -> hipError_t {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dl);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3(grid_used), dim3(block_used), dl, h->stream, h->W, PR, B, (int)E);
-      return hipGetLastError();
-    };
-    if (quad) le = jd == 1 ? launch_trio(rrt_trio_kernel<1, 4>) : (jd == 2 ? launch_trio(rrt_trio_kernel<2, 4>) : launch_trio(rrt_trio_kernel<4, 4>));
-    else le = jd == 1 ? launch_trio(rrt_trio_kernel<1, 3>) : (jd == 2 ? launch_trio(rrt_trio_kernel<2, 3>) : launch_trio(rrt_trio_kernel<4, 3>));
-  } else if (use_duo) {
-    int eps_wg = (E + n_cu_ - 1) / n_cu_;
-    eps_wg = eps_wg < 1 ? 1 : (eps_wg > DUO_EP ? DUO_EP : eps_wg);
-    const int jd = O_ <= 64 ? 1 : (O_ <= 128 ? 2 : 4);
-    const int dl = duo_lds_bytes(P.K, h->max_pts, jd * 64, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), eps_wg);
-    if (dl > 160 * 1024) return fail(h, AUVP_ERR_ARG, "LDS need %d B > 160 KiB (K=%d)", dl, P.K);
-    grid_used = (E + eps_wg - 1) / eps_wg; block_used = eps_wg * 128; lds_used = dl;
-    auto launch_duo = [&](auto kern) -> hipError_t {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dl);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3(grid_used), dim3(block_used), dl, h->stream, h->W, PR, B, (int)E, h->max_pts);
-      return hipGetLastError();
-    };
-    le = jd == 1 ? launch_duo(rrt_duo_kernel<1>) : (jd == 2 ? launch_duo(rrt_duo_kernel<2>) : launch_duo(rrt_duo_kernel<4>));
-  } else if (use_rows) {
-    // a workgroup of up to 12 waves (48 episodes) fills one CU; a batch that cannot give every CU such a workgroup is
-    // spread over all CUs with fewer waves per workgroup instead of leaving CUs idle
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-    if (n_cu <= 0) n_cu = 256;
-    // (option ROWS_WG_WAVES: the waves per workgroup instead, both forms of the kernel -- tests: small batches at the shapes
-    // only full-chip batches get otherwise)
-    int wg_waves = (int)h->opt_num(OPT_ROWS_WG_WAVES, (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu));
-    wg_waves = wg_waves < 1 ? 1 : (wg_waves > RW_WAVES ? RW_WAVES : wg_waves);
-    const RowsLdsPlan rq = rrt_rows_lds_plan(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), wg_waves);
-    const int per_wg = wg_waves * RW_ROWS;
-    grid_used = (E + per_wg - 1) / per_wg; block_used = wg_waves * 64; lds_used = rq.total;
-    // round 6: the episodes' random() numbers generated AHEAD by a launch of its own (rrt_stream_kernel.h: one wavefront per
-    // episode, every lane busy) and read by rrt_rows_stream_kernel -- no generator, no tempering, 2.5 KB less LDS per episode in
-    // the expansion kernel.  Measured on the headline batch: the expansion launch 93.7 -> 81.5 ms (953 instead of 1 284 vector
-    // instructions per trip), generating 46 GB of numbers ahead 9.4 ms, the pass 99.6 -> 96.9 ms (profiles/r6_rows_stream.md).
-    // The stream's length is a bound, and how many numbers an iteration draws depends on the PARAMETERS (44.8 with the bench's,
-    // 92 with the leaves looked at every iteration) and hardly on the world (bench world, 64 / 256 obstacles, dense boxes,
-    // concave outlines, accept rates 0.54 .. 0.99: the busiest of 1 024 episodes draws 45.56 .. 45.86 per iteration at 10 000
-    // iterations, profiles/r6_rows_stream.md): it is set from what earlier batches with the same parameter block drew -- the
-    // busiest episode seen + 3 % + 1 024 numbers (rrt_leaf_kernel reports the figure: leaf_stats[4]) -- whatever world they
-    // ran on, so a caller that replans on a changing world (replanning: rrt_dubins.py:297-331) is served as well.  The first
-    // batch with a parameter block runs rrt_rows_kernel and the following ones this path; an episode that runs past its
-    // stream all the same is reported through the mapped flag and auvp_rrt_run redoes the batch with the kernel above (which
-    // records the new figure).  Option ROWS_STREAM = 0: never; = 1: also without a previous batch (46.5 numbers
-    // per iteration + 4 096), and a stream that does not fit the free memory beside a 4 GB margin is an error instead of a
-    // quiet no; ROWS_STREAM_CAP: the length in numbers (tests).
-    // (a batch at most four times the size of the one the figure comes from: the busiest of more episodes is busier)
-    const auvp_handle::Drawn* seen = h->drawn_find(P);
-    if (seen && (long long)seen->E * 4 < E) seen = nullptr;
-    bool use_stream = !no_stream && P.max_iter >= 16 && h->opt_flag(OPT_ROWS_STREAM, seen != nullptr && P.max_iter >= 1000);
-    long long cap = 0;
-    bool grew = false;
-    if (use_stream) {
-      cap = rrt_stream_len(h, seen);
-      if (cap > 0x7fffffffll) use_stream = false;  // (positions are 32-bit in the kernel)
-      else if (!rrt_stream_reserve(h, (size_t)E * (size_t)cap * sizeof(double), &grew)) {
-        if (h->opt_on(OPT_ROWS_STREAM)) return fail(h, AUVP_ERR_CAPACITY, "ROWS_STREAM = 1: %zu bytes of random stream do not fit the free memory", (size_t)E * (size_t)cap * sizeof(double));
-        use_stream = false;
-      }
-    }
-    if (grew) HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (the allocation is not part of the pass's time: nothing was launched yet)
-    if (use_stream) {
+  const int E = h->E, O = h->W.n_obstacles, max_pts = h->max_pts;
+  auto launch = [&](auto kern, const auto&... more) { return launch_kernel(kern, plan.grid, plan.block, plan.lds, h->stream, h->W, PR, B, E, more...); };
+  switch (plan.kind) {
+    case RRT_TRIO:
+      return for_obstacle_J<4>(O, [&](auto j) {
+        constexpr int J = decltype(j)::value;
+        return plan.quad ? launch(rrt_trio_kernel<J, 4>) : launch(rrt_trio_kernel<J, 3>);
+      });
+    case RRT_DUO:
+      return for_obstacle_J<4>(O, [&](auto j) { return launch(rrt_duo_kernel<decltype(j)::value>, max_pts); });
+    case RRT_ROWS:  // (rows_kernels.hip)
+      return auvpi_rrt_rows_launch(&h->W, &PR, &B, E, plan.grid, plan.block, plan.lds_max, plan.lds, h->stream);
+    case RRT_ROWS_STREAM: {
       RrtBuffers Bs = B;
       Bs.stream = h->d_stream.as<double>();
-      Bs.stream_cap = cap;
-      // without the generator's state an episode needs 2.3 KB of LDS instead of 3.3: a CU holds 64 of them -- sixteen wavefronts,
-      // four per SIMD -- but that instantiation spills (rows_kernels.hip): twelve at most, like rrt_rows_kernel (option
-      // ROWS_STREAM_WAVES: fewer, for experiments)
-      int sw = (int)h->opt_num(OPT_ROWS_WG_WAVES, (E + RW_ROWS * n_cu - 1) / (RW_ROWS * n_cu));
-      const int sw_max = (int)h->opt_num(OPT_ROWS_STREAM_WAVES, RW_WAVES);  // (the four-per-SIMD form measured 0.93 G expansions/s against 1.16: 100 B of scratch per lane at 128 registers)
-      sw = sw < 1 ? 1 : (sw > sw_max ? sw_max : sw);
-      // the ring's form: its first 48 entries mirrored behind it (reads at one address per lane plus an immediate: 3 KB per
-      // episode) where that plan fits at the wave count the masked plan (2.8 KB) allows -- never a wavefront fewer for it
-      // (rrt_rows_stream_shape; option ROWS_STREAM_MIRROR = 0 / 1: the masked / the mirrored form whatever the rule says)
-      const RowsStreamShape shape = rrt_rows_stream_shape(P.K, RW_MAX_OBST, rrt_tables_bytes(h->W.n_habitats, h->W.n_poly, h->W.n_bins), sw,
-                                                          h->opt_has[OPT_ROWS_STREAM_MIRROR] ? (h->opt_val[OPT_ROWS_STREAM_MIRROR] != 0 ? 1 : 0) : -1);
-      sw = shape.waves;
-      const RowsStreamLdsPlan sp = shape.plan;
-      const RowsStreamLdsPlan sp_max = sp;
-      h->last_stream_mirror = shape.mirror ? 1 : 0;
-      grid_used = (E + sw * RW_ROWS - 1) / (sw * RW_ROWS); block_used = sw * 64;
-      lds_used = sp.total;
-      h->last_rrt_kernel = "rrt_rows_stream_kernel";
-      h->last_stream_len = cap;
-      le = auvpi_rrt_stream_launch(&Bs, (int)E, h->stream);
-      if (le == hipSuccess) le = hipEventRecord(h->ev_pre, h->stream);
-      if (le == hipSuccess) le = auvpi_rrt_rows_stream_launch(&h->W, &PR, &Bs, (int)E, grid_used, block_used, sp_max.total, sp.total, shape.mirror ? 1 : 0, h->stream);
-      stream_launched = true;
-    } else
-    le = auvpi_rrt_rows_launch(&h->W, &PR, &B, (int)E, grid_used, block_used, rp.total, rq.total, h->stream);  // (rows_kernels.hip)
-  } else {
+      Bs.stream_cap = plan.stream_len;
+      hipError_t e = auvpi_rrt_stream_launch(&Bs, E, h->stream);
+      if (e == hipSuccess) e = hipEventRecord(h->ev_pre, h->stream);
+      if (e == hipSuccess) e = auvpi_rrt_rows_stream_launch(&h->W, &PR, &Bs, E, plan.grid, plan.block, plan.lds_max, plan.lds, plan.mirror, h->stream);
+      return e;
+    }
+    case RRT_EXPLORE_LIM:
+      return for_obstacle_J<16>(O, [&](auto j) { return launch(rrt_explore_lim_kernel<decltype(j)::value>, max_pts, h->d_lim.as<RrtEpisodeLimDev>()); });
+    case RRT_EXPLORE:
+      break;
+  }
   // compile-time specialisation: obstacles per lane (J), parent-sampling mode, diagnostics on/off
-  const int jsel = O <= 64 ? 0 : (O <= 128 ? 1 : (O <= 256 ? 2 : (O <= 512 ? 3 : 4)));
-  const RrtEpisodeLimDev* lim = h->d_lim.as<RrtEpisodeLimDev>();
-  auto launch_lim = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(xw * 64), lds, h->stream, h->W, PR, B, (int)E, h->max_pts, lim);
-    return hipGetLastError();
-  };
-#define AUVP_LAUNCH_J(JV)                                                                   \
-  do {                                                                                      \
-    if (h->lim) le = launch_lim(rrt_explore_lim_kernel<JV>);                                \
-    else if (P.mode == 0) le = diag ? launch(rrt_explore_kernel<JV, 0, true>) : launch(rrt_explore_kernel<JV, 0, false>); \
-    else if (P.mode == 1) le = diag ? launch(rrt_explore_kernel<JV, 1, true>) : launch(rrt_explore_kernel<JV, 1, false>); \
-    else le = diag ? launch(rrt_explore_kernel<JV, 2, true>) : launch(rrt_explore_kernel<JV, 2, false>); \
-  } while (0)
-  switch (jsel) {
-    case 0: AUVP_LAUNCH_J(1); break;
-    case 1: AUVP_LAUNCH_J(2); break;
-    case 2: AUVP_LAUNCH_J(4); break;
-    case 3: AUVP_LAUNCH_J(8); break;
-    default: AUVP_LAUNCH_J(16); break;
+  const bool diag = (PR.flags & (AUVP_FLAG_ITER_LOG | AUVP_FLAG_LEAF_LOG | AUVP_FLAG_PHASE_CLOCKS)) != 0;
+  return for_obstacle_J<16>(O, [&](auto j) {
+    constexpr int J = decltype(j)::value;
+    if (PR.mode == 0) return diag ? launch(rrt_explore_kernel<J, 0, true>, max_pts) : launch(rrt_explore_kernel<J, 0, false>, max_pts);
+    if (PR.mode == 1) return diag ? launch(rrt_explore_kernel<J, 1, true>, max_pts) : launch(rrt_explore_kernel<J, 1, false>, max_pts);
+    return diag ? launch(rrt_explore_kernel<J, 2, true>, max_pts) : launch(rrt_explore_kernel<J, 2, false>, max_pts);
+  });
+}
+
+// the trees are complete: rank the qualifying leaves (same stream, inside the timed region)
+static int rrt_launch_leaf(auvp_handle* h) {
+  const RrtBuffers& B = h->B;
+  const int E = h->E;
+  // dynamic LDS of the leaf pass: the separable-grid edge tables + one "ancestor of a qualifying leaf" bit per node
+  // and episode (trees too large for that are swept whole)
+  const int gl = rrt_leaf_grid_lds_bytes(h->W.sg_enabled, h->W.sg_ncol, h->W.sg_nrow);
+  // (option LEAF_SWEEP_ALL: no pruning, every node visited -- what trees of more than 131 072 nodes get; for tests)
+  const int bm_words = h->opt_on(OPT_LEAF_SWEEP_ALL) ? 0 : rrt_leaf_mark_words(B.cap_nodes);
+  const int dyn = gl + RRT_LEAF_WAVES * bm_words * 4;
+  const int grid = (E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES;
+  if (h->lim) HIPCHK(h, launch_kernel(rrt_leaf_lim_kernel, grid, RRT_LEAF_WAVES * 64, dyn, h->stream, h->W, h->P, B, E, bm_words, h->d_lim.as<RrtEpisodeLimDev>()));
+  else HIPCHK(h, launch_kernel(rrt_leaf_kernel, grid, RRT_LEAF_WAVES * 64, dyn, h->stream, h->W, h->P, B, E, bm_words));
+  return AUVP_OK;
+}
+
+// what the pass that just completed drew (the most 32-bit outputs of one episode, in the mapped page beside the pipeline flag):
+// kept per parameter block for the length of the next batch's stream
+static void rrt_record_drawn(auvp_handle* h, const RrtLaunchPlan& plan) {
+  const RrtParamsDev& P = h->P;
+  unsigned long long d32 = 0;
+  memcpy(&d32, h->pipe_fail_host + 2, sizeof d32);
+  if (d32 == 0) return;
+  // (the most seen with these parameters: worlds that alternate between a little more and a little less do not make every
+  // other batch run past its stream; a parameter block not seen before takes the slot used longest ago)
+  auvp_handle::Drawn* d = h->drawn_find(P);
+  const long long now = (long long)((d32 + 1) / 2);
+  if (!d) {
+    d = &h->drawn[0];
+    for (auvp_handle::Drawn& x : h->drawn)
+      if (!x.valid || (d->valid && x.used < d->used)) d = &x;
+    *d = auvp_handle::Drawn{};
+    d->P = P;
+    d->valid = true;
   }
-#undef AUVP_LAUNCH_J
+  d->most = d->most > now ? d->most : now;
+  d->E = d->E > h->E ? d->E : h->E;
+  d->used = ++h->drawn_clock;
+  // the next batch with these parameters will want its stream: the buffer is taken NOW, in the call that found
+  // out (tens of GB: a second of hipMalloc that a later, timed call would pay otherwise)
+  if (plan.kind == RRT_ROWS && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true)) {
+    const long long cap_next = rrt_stream_len(h->opt, d->most, P.max_iter);
+    if (cap_next <= 0x7fffffffll) (void)rrt_stream_reserve(h, (size_t)h->E * (size_t)cap_next * sizeof(double));
   }
-  HIPCHK(h, le);
-  // the trees are complete: rank the qualifying leaves (same stream, inside the timed region)
-  HIPCHK(h, hipEventRecord(h->ev_mid, h->stream));
-  {
-    // dynamic LDS of the leaf pass: the separable-grid edge tables + one "ancestor of a qualifying leaf" bit per node
-    // and episode (trees too large for that are swept whole)
-    const int gl = rrt_leaf_grid_lds_bytes(h->W.sg_enabled, h->W.sg_ncol, h->W.sg_nrow);
-    // (option LEAF_SWEEP_ALL: no pruning, every node visited -- what trees of more than 131 072 nodes get; for tests)
-    const int bm_words = h->opt_on(OPT_LEAF_SWEEP_ALL) ? 0 : rrt_leaf_mark_words(B.cap_nodes);
-    const int dyn = gl + RRT_LEAF_WAVES * bm_words * 4;
-    if (h->lim) {
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(rrt_leaf_lim_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
-      hipLaunchKernelGGL(rrt_leaf_lim_kernel, dim3((E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES), dim3(RRT_LEAF_WAVES * 64), dyn, h->stream,
-                         h->W, P, B, (int)E, bm_words, h->d_lim.as<RrtEpisodeLimDev>());
-    } else {
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(rrt_leaf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
-      hipLaunchKernelGGL(rrt_leaf_kernel, dim3((E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES), dim3(RRT_LEAF_WAVES * 64), dyn, h->stream,
-                         h->W, P, B, (int)E, bm_words);
-    }
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  // (the most 32-bit outputs one episode drew: eight bytes into the mapped page beside the pipeline flag)
-  // (not from a batch with per-episode limits: the figure sizes streams of plain batches with the same parameter block)
-  const bool want_drawn = B.leaf_stats && h->pipe_fail_host && !h->lim;
-  if (want_drawn) HIPCHK(h, hipMemcpyAsync(h->pipe_fail_host + 2, B.leaf_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (want_drawn && !h->pipe_failed()) {
-    unsigned long long d32 = 0;
-    memcpy(&d32, h->pipe_fail_host + 2, sizeof d32);
-    if (d32 > 0) {
-      // (the most seen with these parameters: worlds that alternate between a little more and a little less do not make every
-      // other batch run past its stream; a parameter block not seen before takes the slot used longest ago)
-      auvp_handle::Drawn* d = h->drawn_find(P);
-      const long long now = (long long)((d32 + 1) / 2);
-      if (!d) {
-        d = &h->drawn[0];
-        for (auvp_handle::Drawn& x : h->drawn)
-          if (!x.valid || (d->valid && x.used < d->used)) d = &x;
-        *d = auvp_handle::Drawn{};
-        d->P = P;
-        d->valid = true;
-      }
-      d->most = d->most > now ? d->most : now;
-      d->E = d->E > E ? d->E : E;
-      d->used = ++h->drawn_clock;
-      // the next batch with these parameters will want its stream: the buffer is taken NOW, in the call that found
-      // out (tens of GB: a second of hipMalloc that a later, timed call would pay otherwise)
-      if (use_rows && !stream_launched && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true)) {
-        const long long cap_next = rrt_stream_len(h, d);
-        if (cap_next <= 0x7fffffffll) (void)rrt_stream_reserve(h, (size_t)E * (size_t)cap_next * sizeof(double));
-      }
-    }
-  }
+}
+
+// HIP-event times of the pass: whole, [stream generator,] expansion, leaf
+static int rrt_record_times(auvp_handle* h, bool stream_launched) {
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms;
@@ -1148,8 +961,61 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   }
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev_mid, h->ev1));
   h->last_leaf_ms = ms;
-  h->last_rows = use_rows ? 1 : 0;
-  h->last_grid = grid_used; h->last_block = block_used; h->last_lds = lds_used;
+  return AUVP_OK;
+}
+
+// one pass over the prepared batch: the expansion launch rrt_choose_launch names (launch_plan.h) + the leaf pass.
+// one_wave_only: never a speculative pipeline; no_stream: the random numbers are generated inside the expansion kernel whatever
+// option ROWS_STREAM says (the stream fallback)
+static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = false) {
+  const RrtParamsDev& P = h->P;
+  const RrtBuffers& B = h->B;
+  const int E = h->E;
+  RrtLaunchIn in;
+  in.E = E; in.n_cu = h->n_cu;
+  in.mode = P.mode; in.max_iter = P.max_iter; in.K = P.K; in.flags = P.flags; in.freq = P.freq; in.dist_to_end = P.dist_to_end;
+  in.max_pts = h->max_pts;
+  in.O = h->W.n_obstacles; in.H = h->W.n_habitats; in.V = h->W.n_poly; in.T = h->W.n_bins; in.obst_area = h->obst_area;
+  in.lim = h->lim; in.one_wave_only = one_wave_only; in.no_stream = no_stream;
+  if (const auvp_handle::Drawn* seen = h->drawn_find(P)) { in.seen_most = seen->most; in.seen_E = seen->E; }
+  RrtLaunchPlan plan = rrt_choose_launch(in, h->opt);
+  h->last_stream_mirror = -1;
+  h->last_stream_ms = 0.0;
+  h->last_stream_len = 0;
+  if (plan.status == PLAN_LDS_ONE_WAVE)
+    return fail(h, AUVP_ERR_ARG, "LDS need %zu B > 160 KiB (K=%d, freq=%d)", (size_t)plan.lds_need, P.K, (int)std::floor(P.freq));
+  if (plan.status != PLAN_OK) return fail(h, AUVP_ERR_ARG, "LDS need %d B > 160 KiB (K=%d)", (int)plan.lds_need, P.K);
+  if (B.leaf_stats) HIPCHK(h, hipMemsetAsync(B.leaf_stats, 0, 8 * sizeof(unsigned long long), h->stream));  // (before the timed region)
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  if (plan.kind == RRT_ROWS_STREAM) {
+    const size_t bytes = (size_t)E * (size_t)plan.stream_len * sizeof(double);
+    bool grew = false;
+    if (!rrt_stream_reserve(h, bytes, &grew)) {
+      if (h->opt_on(OPT_ROWS_STREAM)) return fail(h, AUVP_ERR_CAPACITY, "ROWS_STREAM = 1: %zu bytes of random stream do not fit the free memory", bytes);
+      in.no_stream = true;
+      plan = rrt_choose_launch(in, h->opt);
+    }
+    if (grew) HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (the allocation is not part of the pass's time: nothing was launched yet)
+  }
+  const bool stream_launched = plan.kind == RRT_ROWS_STREAM;
+  if (stream_launched) { h->last_stream_mirror = plan.mirror; h->last_stream_len = plan.stream_len; }
+  h->last_rrt_kernel = plan.name;
+  RrtParamsDev PR = P;
+  PR.flags |= plan.kflags;
+  HIPCHK(h, rrt_launch_expansion(h, plan, PR));
+  HIPCHK(h, hipEventRecord(h->ev_mid, h->stream));
+  int rc = rrt_launch_leaf(h);
+  if (rc != AUVP_OK) return rc;
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  // (the most 32-bit outputs one episode drew: eight bytes into the mapped page beside the pipeline flag)
+  // (not from a batch with per-episode limits: the figure sizes streams of plain batches with the same parameter block)
+  const bool want_drawn = B.leaf_stats && h->pipe_fail_host && !h->lim;
+  if (want_drawn) HIPCHK(h, hipMemcpyAsync(h->pipe_fail_host + 2, B.leaf_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (want_drawn && !h->pipe_failed()) rrt_record_drawn(h, plan);
+  if ((rc = rrt_record_times(h, stream_launched))) return rc;
+  h->last_rows = plan.rows() ? 1 : 0;
+  h->last_grid = plan.grid; h->last_block = plan.block; h->last_lds = plan.lds;
   h->have_batch = true;
   return AUVP_OK;
 }
@@ -1340,6 +1206,49 @@ int auvp_rrt_rows_stream_shape(int32_t K, int32_t n_habitats, int32_t n_poly, in
   return AUVP_OK;
 }
 
+// the options a query names, as the view the choice reads; false: an unknown name
+static bool query_options(int32_t n, const char* const* names, const int64_t* values, OptionView* opt) {
+  if (n < 0 || (n > 0 && (!names || !values))) return false;
+  for (int i = 0; i < n; i++) {
+    const int k = names[i] ? auvp_option_index(names[i]) : -1;
+    if (k < 0) return false;
+    opt->opt_has[k] = true; opt->opt_val[k] = values[i];
+  }
+  return true;
+}
+
+int auvp_rrt_choose_launch(const auvp_rrt_launch_query* q, auvp_rrt_launch_choice* c) {
+  OptionView opt;
+  if (!q || !c || q->n_episodes <= 0 || q->n_cu <= 0 || q->n_obstacles < 0 || q->n_habitats < 0 || q->n_poly < 0 || q->n_bins < 0 ||
+      q->n_time_bins < 0 || !query_options(q->n_options, q->option_names, q->option_values, &opt))
+    return AUVP_ERR_ARG;
+  RrtLaunchIn in;
+  in.E = q->n_episodes; in.n_cu = q->n_cu;
+  in.mode = q->mode; in.max_iter = q->max_iter; in.K = q->n_time_bins; in.flags = q->flags; in.freq = q->freq; in.dist_to_end = q->dist_to_end;
+  in.max_pts = q->max_pts;
+  in.O = q->n_obstacles; in.H = q->n_habitats; in.V = q->n_poly; in.T = q->n_bins; in.obst_area = q->obst_area;
+  in.lim = q->per_episode_limits != 0; in.one_wave_only = q->one_wave_only != 0; in.no_stream = q->no_stream != 0;
+  in.seen_most = q->seen_most; in.seen_E = q->seen_E;
+  const RrtLaunchPlan p = rrt_choose_launch(in, opt);
+  *c = auvp_rrt_launch_choice{p.status == PLAN_OK ? AUVP_OK : AUVP_ERR_ARG, (int32_t)p.kind, p.J, p.quad ? 1 : 0, p.grid, p.block, p.lds, p.lds_max,
+                              p.kflags, p.stream_waves, p.mirror, 0, p.stream_len, p.lds_need, p.name};
+  return AUVP_OK;
+}
+
+int auvp_prrt_choose_launch(const auvp_prrt_launch_query* q, auvp_prrt_launch_choice* c) {
+  OptionView opt;
+  if (!q || !c || q->n_episodes <= 0 || q->n_cu <= 0 || q->n_obstacles < 0 || !query_options(q->n_options, q->option_names, q->option_values, &opt))
+    return AUVP_ERR_ARG;
+  PrrtLaunchIn in;
+  in.E = q->n_episodes; in.n_cu = q->n_cu; in.O = q->n_obstacles; in.freq = q->freq;
+  in.max_pts = q->max_pts; in.cap_nodes = q->cap_nodes; in.n_buckets = q->n_buckets; in.max_step = q->max_step; in.flags = q->flags;
+  in.step_mode = q->step_mode; in.waits = q->waits != 0; in.one_wave_only = q->one_wave_only != 0; in.rows = q->rows;
+  const PrrtLaunchPlan p = prrt_choose_launch(in, opt);
+  *c = auvp_prrt_launch_choice{p.status == PLAN_OK ? AUVP_OK : AUVP_ERR_ARG, (int32_t)p.kind, p.lat, p.rows, p.pipe, p.draw_wave, p.next_lds, p.bk_lds,
+                               p.obst_lds, p.eps_wg, p.grid, p.block, p.lds, p.J, p.lds_need, p.name};
+  return AUVP_OK;
+}
+
 int auvp_rrt_last_leaf_stats(auvp_handle* h, int64_t* out4) {
   if (!h || !out4) return AUVP_ERR_ARG;
   if (!h->have_batch || !h->B.leaf_stats) return fail(h, AUVP_ERR_STATE, "no batch has run");
@@ -1359,10 +1268,6 @@ int auvp_last_launch(auvp_handle* h, int32_t* grid, int32_t* block, int32_t* lds
 }  // extern "C"
 
 #include "probe_kernels.h"
-#include "planner_rrt_kernel.h"
-#include "planner_rows_kernel.h"
-#include "planner_goal_arc.h"
-#include "planner_pipe_kernel.h"
 #include "planner_rrt_host.h"
 
 namespace {

@@ -46,53 +46,33 @@ extern "C" hipError_t auvpi_prrt_rows_launch(int obst_lds, const auvp::WorldDev*
                                              hipStream_t stream);
 namespace {
 
+// what prrt_choose_launch (launch_plan.h) reads of a batch; rows: -1 decide the four-episode choice, else the batch's frozen value
+auvp::PrrtLaunchIn prrt_launch_in(const auvp_handle* h, const PrrtState& S, int E, int rows) {
+  auvp::PrrtLaunchIn in;
+  in.E = E; in.n_cu = h->n_cu; in.O = h->W.n_obstacles; in.freq = S.P.freq;
+  in.max_pts = S.B.max_pts; in.cap_nodes = S.B.cap_nodes;
+  in.n_buckets = S.P.n_buckets; in.max_step = S.P.max_step; in.flags = S.P.flags;
+  in.rows = rows;
+  return in;
+}
+
 // `sync`: wait for the launch and record its HIP-event time (the device-resident loop passes false: it only enqueues)
 int prrt_launch(auvp_handle* h, PrrtState& S, int step_mode, bool sync = true, bool one_wave_only = false) {
   S.P.step_mode = step_mode;
   if (!one_wave_only) { h->pipe_clear(); h->pipe_fallback_last = 0; }
-  const int nfreq = (int)std::floor(S.P.freq);
-  // latency run (at most three waves per SIMD on this GPU) or throughput run: register budget and steer differ (planner_rrt_kernel.h)
-  int n_cu_l = 256;
-  (void)hipDeviceGetAttribute(&n_cu_l, hipDeviceAttributeMultiprocessorCount, h->device);
-  if (n_cu_l <= 0) n_cu_l = 256;
-  const bool lat = h->opt_flag(OPT_PRRT_LAT, S.E <= 12 * n_cu_l);  // (12: see prrt_create_batch's choice of the four-episode kernel)
-  // latency runs: workgroups small enough that every CU gets one (512 episodes: 256 workgroups of two waves)
-  int wg_waves = auvp::RRT_WAVES;
-  if (lat) { wg_waves = (S.E + n_cu_l - 1) / n_cu_l; wg_waves = wg_waves < 1 ? 1 : (wg_waves > auvp::RRT_WAVES ? auvp::RRT_WAVES : wg_waves); }
-  const int grid = (S.E + wg_waves - 1) / wg_waves;
-  const size_t lds = (size_t)wg_waves * auvp::prrt_lds_per_wave(S.B.max_pts, nfreq, lat);
-  if (lds > 160 * 1024) return fail(h, AUVP_ERR_ARG, "LDS need %zu B > 160 KiB", lds);
+  auvp::PrrtLaunchIn in = prrt_launch_in(h, S, S.E, S.use_rows ? 1 : 0);
+  in.step_mode = step_mode; in.waits = sync; in.one_wave_only = one_wave_only;
+  const auvp::PrrtLaunchPlan plan = auvp::prrt_choose_launch(in, h->opt);
+  if (plan.status != auvp::PLAN_OK) return fail(h, AUVP_ERR_ARG, "LDS need %zu B > 160 KiB", (size_t)plan.lds_need);
   const int O = h->W.n_obstacles;
-  auto launch = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(wg_waves * 64), lds, h->stream, h->W, S.P, S.B, S.E);
-    return hipGetLastError();
+  auto launch = [&](auto kern, const auto&... more) {
+    return launch_kernel(kern, plan.grid, plan.block, plan.lds, h->stream, h->W, S.P, S.B, S.E, more...);
   };
   if (sync) HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (enqueue-only calls may be under stream capture: no events)
   hipError_t le;
-  int grid_used = grid, block_used = wg_waves * 64;
-  size_t lds_used = lds;
-  S.last_kernel = "prrt_kernel";
-  // plan-mode latency runs of at most four episodes per CU: a pipeline of four wavefronts per episode (planner_pipe_kernel.h).
-  // Option PRRT_PIPE = 0 / 1 forces the choice where the kernel's limits allow it.  Only where this call waits for the launch:
-  // the pipeline is speculative and an episode it gives up on is redone on prrt_kernel below (pipeline fallback).
-  const bool use_pipe = sync && !one_wave_only && !S.use_rows && step_mode == 0 && lat && !(S.P.flags & AUVP_FLAG_ITER_LOG) &&
-                        nfreq <= auvp::DUO_MAX_FREQ && O <= 256 && S.B.max_pts <= auvp::DUO_CS + 2 && h->opt_flag(OPT_PRRT_PIPE, S.E <= 4 * n_cu_l);
-  if (S.use_rows) {
-    // persistent rows (four episodes per wavefront) fed from a device counter: as many workgroups as fit the chip at
-    // three per CU (one wave per SIMD each), fewer when the batch is smaller
-    S.last_kernel = "prrt_rows_kernel";
-    const int per_wg = auvp::PRW_WAVES * auvp::RW_ROWS;
-    grid_used = std::min((S.E + per_wg - 1) / per_wg, 3 * n_cu_l);
-    block_used = auvp::PRW_WAVES * 64;
-    const int occ_bytes = auvp::prrt_rows_occ_bytes(S.P.n_buckets, S.P.max_step);
-    lds_used = (size_t)per_wg * (auvp::PRW_LDS_PER_EP + occ_bytes);
-    // the obstacle slot tables as an LDS tile where three workgroups per CU still fit beside it (option PRRT_OBST_LDS overrides)
-    // (LDS is handed out in 1 280-byte granules on this GPU: three workgroups of 53 760 B fit a CU, three of 54 272 B do not)
-    auto granules = [](size_t b) { return (b + 1279) / 1280 * 1280; };
-    const bool obst_lds = h->opt_flag(OPT_PRRT_OBST_LDS, 3 * granules(lds_used + auvp::PRW_OBST_TILE) <= (size_t)160 * 1024);
-    if (obst_lds) lds_used += auvp::PRW_OBST_TILE;
+  S.last_kernel = plan.name;
+  switch (plan.kind) {
+  case auvp::PRRT_ROWS: {
     // The ids a launch hands out are counter - work_base.  Eager launches carry the base as an argument (no memset per
     // launch).  A launch recorded into a hipGraph would freeze that argument while the counter keeps advancing on every
     // replay, so from the first capture on this state zeroes the counter with a memset NODE in front of every launch and
@@ -111,32 +91,14 @@ int prrt_launch(auvp_handle* h, PrrtState& S, int step_mode, bool sync = true, b
     } else le = hipSuccess;
     if (le == hipSuccess) {
       // (the kernel lives in prrt_rows_kernels.hip: a translation unit with its own compiler flags)
-      le = auvpi_prrt_rows_launch(obst_lds ? 1 : 0, &h->W, &S.P, &S.B, S.E, S.work.as<int>(), S.work_base, occ_bytes, grid_used, block_used,
-                                  (int)lds_used, h->stream);
+      le = auvpi_prrt_rows_launch(plan.obst_lds ? 1 : 0, &h->W, &S.P, &S.B, S.E, S.work.as<int>(), S.work_base, plan.occ_bytes, plan.grid,
+                                  plan.block, plan.lds, h->stream);
       // every episode once + one empty pull per row; a failed launch pulled nothing, a memset-fronted one restarts at 0
-      if (le == hipSuccess && !S.work_memset) S.work_base += S.E + grid_used * per_wg;
+      if (le == hipSuccess && !S.work_memset) S.work_base += S.E + plan.grid * plan.eps_wg;
     }
-  } else if (use_pipe) {
-    // four wavefronts per episode, feed-forward (planner_pipe_kernel.h)
-    S.last_kernel = "prrt_pipe_kernel";
-    int eps_wg = (S.E + n_cu_l - 1) / n_cu_l;
-    eps_wg = eps_wg < 1 ? 1 : (eps_wg > auvp::PPIPE_EP ? auvp::PPIPE_EP : eps_wg);
-    // round 6: a FIFTH wavefront per episode takes the sub-arc draws off H, the slowest stage (planner_pipe_kernel.h: D) -- where
-    // a workgroup of five-wavefront episodes fits the 1 024-thread limit (at most three episodes per workgroup: up to 768
-    // episodes on this GPU; config 4's 512 run two per CU).  Option PRRT_PIPE_DRAW = 0 / 1 forces the choice within that limit.
-    const bool draw_wave = eps_wg <= auvp::PPIPE_EP5 && h->opt_flag(OPT_PRRT_PIPE_DRAW, true);
-    grid_used = (S.E + eps_wg - 1) / eps_wg;
-    block_used = eps_wg * (draw_wave ? 320 : 256);
-    // the member lists' next links in LDS where they fit beside the slots (option PRRT_NEXT_LDS = 0 keeps them in memory)
-    int next_lds = (size_t)eps_wg * auvp::ppipe_per_episode_bytes(S.B.max_pts, S.B.cap_nodes) <= (size_t)150 * 1024 ? 1 : 0;
-    next_lds = next_lds && h->opt_flag(OPT_PRRT_NEXT_LDS, true);
-    // round 6: ... and the bucket table + the occupied list, where they fit too (config 4: 1 600 buckets = 19 KB per episode;
-    // option PRRT_BUCKET_LDS = 0 keeps them in memory)
-    const int occ_cap = auvp::ppipe_occ_entries(S.P.n_buckets, S.B.cap_nodes);
-    int bk_lds = (size_t)eps_wg * auvp::ppipe_per_episode_bytes(S.B.max_pts, next_lds ? S.B.cap_nodes : 0, S.P.n_buckets, occ_cap) <= (size_t)150 * 1024 ? 1 : 0;
-    bk_lds = bk_lds && h->opt_flag(OPT_PRRT_BUCKET_LDS, true);
-    lds_used = (size_t)eps_wg * auvp::ppipe_per_episode_bytes(S.B.max_pts, next_lds ? S.B.cap_nodes : 0, bk_lds ? S.P.n_buckets : 0, bk_lds ? occ_cap : 0);
-    next_lds |= bk_lds << 1;  // (one kernel argument: bit 0 the links, bit 1 the bucket table)
+    break;
+  }
+  case auvp::PRRT_PIPE: {
     // what the fallback needs to take an episode back to where this launch found it: its record, generator and position
     le = S.snap_sum.reserve((size_t)S.E * sizeof(auvp::PrrtSummary));
     if (le == hipSuccess) le = S.snap_rng.reserve((size_t)S.E * 4 * sizeof(int32_t));
@@ -147,43 +109,29 @@ int prrt_launch(auvp_handle* h, PrrtState& S, int step_mode, bool sync = true, b
                        S.snap_rng.as<int32_t>(), S.snap_mt.as<uint32_t>());
     HIPCHK(h, hipGetLastError());
     // (ev0 was recorded before the snapshot: the time a caller is told includes it -- every latency-path plan call pays it)
-    auto launch_pipe = [&](auto kern) -> hipError_t {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3(grid_used), dim3(block_used), lds_used, h->stream, h->W, S.P, S.B, S.E, next_lds);
-      return hipGetLastError();
-    };
-    if (draw_wave) {
-      if (O <= 64) le = launch_pipe(auvp::prrt_pipe_kernel<1, 5>);
-      else if (O <= 128) le = launch_pipe(auvp::prrt_pipe_kernel<2, 5>);
-      else le = launch_pipe(auvp::prrt_pipe_kernel<4, 5>);
-    } else {
-      if (O <= 64) le = launch_pipe(auvp::prrt_pipe_kernel<1, 4>);
-      else if (O <= 128) le = launch_pipe(auvp::prrt_pipe_kernel<2, 4>);
-      else le = launch_pipe(auvp::prrt_pipe_kernel<4, 4>);
-    }
-  } else if (lat) {
-    if (O <= 64) le = launch(auvp::prrt_kernel<1, true>);
-    else if (O <= 128) le = launch(auvp::prrt_kernel<2, true>);
-    else if (O <= 256) le = launch(auvp::prrt_kernel<4, true>);
-    else if (O <= 512) le = launch(auvp::prrt_kernel<8, true>);
-    else le = launch(auvp::prrt_kernel<16, true>);
-  } else {
-    if (O <= 64) le = launch(auvp::prrt_kernel<1, false>);
-    else if (O <= 128) le = launch(auvp::prrt_kernel<2, false>);
-    else if (O <= 256) le = launch(auvp::prrt_kernel<4, false>);
-    else if (O <= 512) le = launch(auvp::prrt_kernel<8, false>);
-    else le = launch(auvp::prrt_kernel<16, false>);
+    const int in_lds = (plan.next_lds ? 1 : 0) | (plan.bk_lds ? 2 : 0);  // (one kernel argument: bit 0 the links, bit 1 the bucket table)
+    le = auvp::for_obstacle_J<4>(O, [&](auto j) {
+      constexpr int J = decltype(j)::value;
+      return plan.draw_wave ? launch(auvp::prrt_pipe_kernel<J, 5>, in_lds) : launch(auvp::prrt_pipe_kernel<J, 4>, in_lds);
+    });
+    break;
+  }
+  case auvp::PRRT_ONE:
+    le = auvp::for_obstacle_J<16>(O, [&](auto j) {
+      constexpr int J = decltype(j)::value;
+      return plan.lat ? launch(auvp::prrt_kernel<J, true>) : launch(auvp::prrt_kernel<J, false>);
+    });
+    break;
   }
   HIPCHK(h, le);
   if (sync) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  h->last_grid = grid_used; h->last_block = block_used; h->last_lds = (int)lds_used;
+  h->last_grid = plan.grid; h->last_block = plan.block; h->last_lds = plan.lds;
   if (!sync) return AUVP_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms;
-  if (use_pipe && h->pipe_failed()) {
+  if (plan.pipe && h->pipe_failed()) {
     // some episode's pipeline gave up (AUVP_ERR_PIPELINE): those episodes go back to where this launch found them (record,
     // generator, bucket table; the tree is append-only) and are planned by the one-wavefront kernel -- the others, finished, are
     // not touched (redo_mask).  Option PIPE_FALLBACK = 0 leaves the status in the summaries instead.
@@ -274,19 +222,8 @@ static int prrt_configure(auvp_handle* h, PrrtState& S, int32_t E, const auvp_pr
     HIPCHK(h, hipMemsetAsync(S.st_log.p, 0xff, (size_t)E * p->max_step * 8 * sizeof(int32_t), h->stream));
     B.st_log = S.st_log.as<int32_t>();
   }
-  {
-    // throughput batches (more than twelve episodes per CU) of the environment's planner shape run four episodes per
-    // wavefront (planner_rows_kernel.h); option PRRT_ROWS = 0 / 1 forces the choice where the kernel's limits allow it.
-    // (Twelve: re-measured at the end of round 6 on config 4's world, M steps/s one wavefront per episode (latency
-    // instantiation) / four episodes per wavefront: 2 048 episodes 276 / 178, 3 072: 334 / 262, 4 096: 311 / 342, 8 192: 359 / 588
-    // -- tools/prrt_batch_probe.py; the threshold had been eight per CU.)
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-    if (n_cu <= 0) n_cu = 256;
-    const bool rows_ok = nfreq <= auvp::PRW_MAX_FREQ && h->W.n_obstacles <= auvp::RW_MAX_OBST && !(flags & AUVP_FLAG_ITER_LOG);
-    const bool lat = h->opt_flag(OPT_PRRT_LAT, E <= 12 * n_cu);
-    S.use_rows = rows_ok && h->opt_flag(OPT_PRRT_ROWS, !lat);
-  }
+  // four episodes per wavefront or one: decided here, once per batch (launch_plan.h)
+  S.use_rows = auvp::prrt_choose_launch(prrt_launch_in(h, S, E, -1), h->opt).rows;
   return AUVP_OK;
 }
 

@@ -235,9 +235,7 @@ int auvp_hbm_probe(auvp_handle* h, uint64_t bytes, int32_t reps, double* read_GB
   unsigned long long nb = (bytes < (64ull << 20) ? (64ull << 20) : bytes) / chunk_b * chunk_b;
   DevBuf buf, sink;
   HIPCHK(h, buf.reserve((size_t)nb));
-  int n_cu = 256;
-  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-  if (n_cu <= 0) n_cu = 256;
+  const int n_cu = h->n_cu;
   const int grid = n_cu * 8;
   HIPCHK(h, sink.reserve((size_t)grid * sizeof(uint32_t)));
   HIPCHK(h, hipMemsetAsync(buf.p, 0x5a, (size_t)nb, h->stream));

@@ -412,6 +412,62 @@ int auvp_rrt_last_stream_mirror(auvp_handle* h);
  * wavefronts per workgroup, the ring's form, the workgroup's LDS bytes.  The rule never gives up a wavefront for the mirror. */
 int auvp_rrt_rows_stream_shape(int32_t K, int32_t n_habitats, int32_t n_poly, int32_t n_bins, int32_t waves_wanted, int32_t force,
                                int32_t* waves, int32_t* mirror, int32_t* lds_bytes);
+/* The whole choice of a launch as a question (no device needed; the library's own launches go through the same rules,
+ * csrc/launch_plan.h): which expansion kernel a batch of RRT.exploring would get, at what shape.  The query describes the batch
+ * (as auvp_rrt_prepare + auvp_world_set would), the device (n_cu compute units) and the options that are SET: n_options names
+ * (without the AUVP_ prefix) and values; an unknown name is AUVP_ERR_ARG.  seen_most / seen_E: what earlier batches with the same
+ * parameter block drew (the most random() numbers of one episode, the largest batch; 0 = nothing seen). */
+typedef struct {
+  int32_t n_episodes, n_cu;
+  int32_t mode, max_iter, n_time_bins /* K = ceil(max_traj_time / bin_interval); 0 outside time-bin mode */, flags /* AUVP_FLAG_* */;
+  double freq, dist_to_end;
+  int32_t max_pts; /* floor(freq) + 2 */
+  int32_t n_obstacles, n_habitats, n_poly, n_bins;
+  double obst_area; /* area of the bounding box of the obstacle centres (0: fewer than two obstacles) */
+  int32_t per_episode_limits, one_wave_only, no_stream; /* auvp_rrt_prepare_episodes; the two fallback passes of auvp_rrt_run */
+  int32_t seen_E;
+  int64_t seen_most;
+  int32_t n_options;
+  const char* const* option_names;
+  const int64_t* option_values;
+} auvp_rrt_launch_query;
+enum { AUVP_RRT_EXPLORE = 0, AUVP_RRT_EXPLORE_LIM, AUVP_RRT_DUO, AUVP_RRT_TRIO, AUVP_RRT_ROWS, AUVP_RRT_ROWS_STREAM };
+typedef struct {
+  int32_t status;    /* AUVP_OK, or AUVP_ERR_ARG: the LDS plan needs lds_need bytes > 160 KiB (auvp_rrt_run fails with that) */
+  int32_t kind;      /* AUVP_RRT_* */
+  int32_t J, quad;   /* obstacles per lane; rrt_trio_kernel with four wavefronts per episode */
+  int32_t grid, block, lds, lds_max; /* lds_max: the kernel's dynamic-LDS attribute */
+  int32_t kflags;    /* 1024: the tight cull, 2048: exact nearest-neighbour ranking */
+  int32_t stream_waves, mirror; /* rrt_rows_stream_kernel: wavefronts per workgroup, the ring's form */
+  int32_t _pad;
+  int64_t stream_len; /* ... random() numbers per episode generated ahead */
+  int64_t lds_need;
+  const char* name;  /* what auvp_rrt_last_kernel would report */
+} auvp_rrt_launch_choice;
+int auvp_rrt_choose_launch(const auvp_rrt_launch_query* query, auvp_rrt_launch_choice* choice);
+/* the same for a launch of Planner_RRT (auvp_prrt_plan: step_mode 0, waits 1; auvp_prrt_step: step_mode 1, waits 1; a step of
+ * the device-resident loop: step_mode 1, waits 0).  rows: -1 decide the four-episode choice as auvp_prrt_create_batch does
+ * (once per batch), 0 / 1 the batch's frozen value. */
+typedef struct {
+  int32_t n_episodes, n_cu, n_obstacles;
+  int32_t max_pts /* floor(freq) + 3 */, cap_nodes /* max_step + 1 */, n_buckets, max_step, flags;
+  double freq;
+  int32_t step_mode, waits, one_wave_only, rows;
+  int32_t n_options, _pad;
+  const char* const* option_names;
+  const int64_t* option_values;
+} auvp_prrt_launch_query;
+enum { AUVP_PRRT_ONE = 0, AUVP_PRRT_PIPE, AUVP_PRRT_ROWS };
+typedef struct {
+  int32_t status;  /* AUVP_OK, or AUVP_ERR_ARG: prrt_kernel's LDS plan needs lds_need bytes > 160 KiB */
+  int32_t kind;    /* AUVP_PRRT_* */
+  int32_t lat, rows, pipe, draw_wave; /* latency batch; four episodes per wavefront; the pipeline; its fifth wavefront */
+  int32_t next_lds, bk_lds, obst_lds; /* pipeline: next links / bucket table in LDS; rows: the obstacle tile in LDS */
+  int32_t eps_wg, grid, block, lds, J;
+  int64_t lds_need;
+  const char* name; /* what auvp_prrt_last_kernel would report */
+} auvp_prrt_launch_choice;
+int auvp_prrt_choose_launch(const auvp_prrt_launch_query* query, auvp_prrt_launch_choice* choice);
 /* name of the expansion kernel the last auvp_rrt_run launched: "rrt_rows_kernel" (four episodes per wavefront: batches of
  * more than 18 episodes per CU; "rrt_rows_stream_kernel": the same with the random numbers generated ahead by
  * rrt_stream_kernel), "rrt_explore_kernel" (one), "rrt_duo_kernel" (two wavefronts per episode: batches of at
