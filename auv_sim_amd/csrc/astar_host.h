@@ -191,6 +191,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
       if (S.visited_set_for != (long long)entries) return fail(h, AUVP_ERR_STATE, "auvp_astar_set_visited not called for this batch shape");
     } else {
       // a fresh visited array = a new epoch; the words are only cleared when the buffer is new or the tag wraps
+      // (255: tests/test_gpu_epoch_wrap.py runs 260 batches on one handle and counts on the wrap falling at batch 256)
       if (S.cellinfo_clean_cap != S.cellinfo.cap || S.epoch >= 255u) {
         HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
         S.cellinfo_clean_cap = S.cellinfo.cap;
@@ -240,6 +241,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
     if (n > 0 && h->opt_flag(OPT_PIPE_FALLBACK, true)) {
       h->pipe_fallback_last = n;
       h->pipe_fallback_total += n;
+      // (255 as above; tests/test_gpu_epoch_wrap.py does not reach this bump: it needs a pipeline that gives up)
       if (S.epoch >= 255u) {
         HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
         S.epoch = 0;
@@ -318,6 +320,7 @@ int auvp_astar_set_visited(auvp_handle* h, int32_t E, int32_t variant, const uin
   HIPCHK(h, hipSetDevice(h->device));
   const size_t entries = (size_t)E * (variant == 2 ? 550 : 600) * 600;
   HIPCHK(h, S.cellinfo.reserve(entries * sizeof(uint32_t)));
+  // (255 as in auvp_astar_batch: tests/test_gpu_epoch_wrap.py, whose bitmaps go in on either side of the wrap)
   if (S.cellinfo_clean_cap != S.cellinfo.cap || S.epoch >= 255u) {
     HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
     S.cellinfo_clean_cap = S.cellinfo.cap;

@@ -20,7 +20,7 @@
   X(ROWS) X(DUO) X(TRIO) X(QUAD) X(TIGHT_CULL) X(NN_EXACT) X(LEAF_SWEEP_ALL) X(NO_HABITAT_GRID) X(RG_MAX_ENTRIES)           \
   X(NO_GRID_INDEX) X(PRRT_LAT) X(PRRT_PIPE) X(PRRT_OBST_LDS) X(PRRT_NEXT_LDS) X(PRRT_ROWS) X(ASTAR_NO_GRID)                 \
   X(ASTAR_NO_LIST) X(ASTAR_PAIR) X(SOG_TILE) X(PIPE_FALLBACK) X(PRRT_PIPE_DRAW) X(PRRT_BUCKET_LDS) X(ROWS_STREAM)           \
-  X(ROWS_STREAM_CAP) X(ROWS_STREAM_WAVES) X(ROWS_WG_WAVES) X(ROWS_STREAM_MIRROR)
+  X(ROWS_STREAM_CAP) X(ROWS_STREAM_WAVES) X(ROWS_WG_WAVES) X(ROWS_STREAM_MIRROR) X(PRRT_ROWS_GRID)
 enum AuvpOpt {
 #define AUVP_OPT_ENUM(n) OPT_##n,
   AUVP_OPTIONS(AUVP_OPT_ENUM)
@@ -320,6 +320,13 @@ inline PrrtLaunchPlan prrt_choose_launch(const PrrtLaunchIn& in, const OptionVie
     p.name = "prrt_rows_kernel";
     p.eps_wg = PRW_WAVES * RW_ROWS;
     p.grid = ceil_div(E, p.eps_wg) < 3 * n_cu ? ceil_div(E, p.eps_wg) : 3 * n_cu;
+    // (option PRRT_ROWS_GRID: at most that many workgroups, at least one -- it only ever lowers the grid, and the kernel has no
+    // waits between workgroups, so any grid >= 1 is valid.  tests: with fewer rows than episodes every batch refills its rows,
+    // which by default depends on timing below 48 episodes per CU)
+    if (opt.opt_has[OPT_PRRT_ROWS_GRID]) {
+      const long long cap = opt.opt_val[OPT_PRRT_ROWS_GRID] < 1 ? 1 : opt.opt_val[OPT_PRRT_ROWS_GRID];
+      if (cap < p.grid) p.grid = (int)cap;
+    }
     p.block = PRW_WAVES * 64;
     p.occ_bytes = prrt_rows_occ_bytes(in.n_buckets, in.max_step);
     p.lds = p.eps_wg * (PRW_LDS_PER_EP + p.occ_bytes);

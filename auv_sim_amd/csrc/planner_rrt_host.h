@@ -234,6 +234,7 @@ static int prrt_plant(auvp_handle* h, PrrtState& S, int32_t E) {
     // every bucket of the new batch is empty: a fresh epoch does that without touching the table (E x n_buckets x 8 bytes);
     // the table itself is cleared when its allocation changed or the 8-bit tag wraps (tag 0 is never current)
     const size_t need = (size_t)E * S.P.n_buckets * sizeof(int2);
+    // (255: tests/test_gpu_epoch_wrap.py runs 260 batches on one handle and counts on the wrap falling at batch 256)
     if (S.bucket_alloc != S.buckets.p || need > S.bucket_alloc_bytes || S.bucket_epoch >= 255) {
       HIPCHK(h, hipMemsetAsync(S.buckets.p, 0, need, h->stream));
       S.bucket_alloc = S.buckets.p; S.bucket_alloc_bytes = need; S.bucket_epoch = 0;

@@ -95,6 +95,8 @@ typedef struct {
   double box[4];     /* variant 0: min_bound.x, min_bound.y, max_bound.x, max_bound.y */
   double limit, velocity;
   double w[4];
+  const uint8_t* visited_in; /* variants 2, 3: [vx,600] self.visited_nodes carried over from earlier astar() calls; NULL: zeros */
+  uint8_t* visited_out;      /* ... the array after this call; NULL: not wanted */
 } orc_astar_params;
 
 typedef struct {

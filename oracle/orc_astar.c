@@ -120,7 +120,8 @@ int orc_astar_run(const orc_world* w, const orc_astar_params* p, orc_astar_out* 
   /* visited bitmap */
   const int VX = (V == 2) ? 550 : 600, VY = 600;
   unsigned char* visited = (V >= 2) ? (unsigned char*)calloc((size_t)VX * VY, 1) : NULL;
-  int visited_count = 0;
+  int visited_count = 0; /* cells this call marks (a carried-over array's marks are not counted again) */
+  if (visited && p->visited_in) memcpy(visited, p->visited_in, (size_t)VX * VY);
   /* SOG tables: rounded cell corners, descending prefix sums of the probabilities per bin */
   const int C = w->n_cells, T = w->n_bins;
   double* rc = NULL;
@@ -256,6 +257,7 @@ int orc_astar_run(const orc_world* w, const orc_astar_params* p, orc_astar_out* 
   o->n_nodes = n_nodes; o->n_expansions = n_exp; o->n_children = n_children; o->found = found >= 0;
   o->visited_count = visited_count; o->path_len = 0; o->smooth_len = 0;
   o->n_hab_left = n_open;
+  if (visited && p->visited_out) memcpy(p->visited_out, visited, (size_t)VX * VY);
   for (int i = 0; i < n_open && o->hab_left; i++) o->hab_left[i] = hopen[i];
   if (found >= 0 && status == ORC_OK) {
     int L = 0;

@@ -11,7 +11,8 @@ VARIANTS = {"astar": 0, "astar_real": 1, "astar_fixLen": 2, "astar_fixLenSOG": 3
 
 class AstarParams(C.Structure):
     _fields_ = [("variant", C.c_int32), ("cap_nodes", C.c_int32), ("start", C.c_double * 2), ("goal", C.c_double * 2),
-                ("box", C.c_double * 4), ("limit", C.c_double), ("velocity", C.c_double), ("w", C.c_double * 4)]
+                ("box", C.c_double * 4), ("limit", C.c_double), ("velocity", C.c_double), ("w", C.c_double * 4),
+                ("visited_in", C.POINTER(C.c_uint8)), ("visited_out", C.POINTER(C.c_uint8))]
 
 
 class AstarOut(C.Structure):
@@ -24,7 +25,9 @@ class AstarOut(C.Structure):
 
 
 def run(variant, start, goal=(0.0, 0.0), obstacles=None, habitats=None, polygon=None, bins=None, cells=None, prob=None,
-        box=(0, 0, 0, 0), limit=0.0, velocity=1.0, weights=(0, 0, 0, 0), cap_nodes=200000, kind="libm"):
+        box=(0, 0, 0, 0), limit=0.0, velocity=1.0, weights=(0, 0, 0, 0), cap_nodes=200000, kind="libm", visited=None):
+    """visited (variants astar_fixLen / astar_fixLenSOG): [550 or 600, 600] uint8, the solver's visited_nodes carried over from
+    earlier astar() calls; the result then holds "visited", the array after this call"""
     L = orc.lib(kind)
     L.orc_astar_run.restype = C.c_int
     L.orc_astar_run.argtypes = [C.POINTER(orc.World), C.POINTER(AstarParams), C.POINTER(AstarOut)]
@@ -48,9 +51,19 @@ def run(variant, start, goal=(0.0, 0.0), obstacles=None, habitats=None, polygon=
     for k in ("exp_log", "path", "cost_list", "node_path", "smooth_path"):
         setattr(o, k, orc._ptr(a[k]))
     o.hab_left = orc._ptr(a["hab_left"], _ip)
+    vis_out = None
+    if visited is not None:
+        vis_in = np.ascontiguousarray(visited, dtype=np.uint8)
+        assert p.variant >= 2 and vis_in.shape == (550 if p.variant == 2 else 600, 600)
+        vis_out = np.zeros_like(vis_in)
+        p.visited_in = vis_in.ctypes.data_as(C.POINTER(C.c_uint8))
+        p.visited_out = vis_out.ctypes.data_as(C.POINTER(C.c_uint8))
     status = L.orc_astar_run(C.byref(w.c), C.byref(p), C.byref(o))
-    return {"status": status, "found": bool(o.found), "n_nodes": o.n_nodes, "n_expansions": o.n_expansions,
-            "n_children": o.n_children, "visited_count": o.visited_count,
-            "expansions": a["exp_log"][:o.n_expansions], "path": a["path"][:o.path_len],
-            "cost_list": a["cost_list"][:o.path_len], "node_path": a["node_path"][:o.path_len],
-            "smooth_path": a["smooth_path"][:o.smooth_len], "hab_left": a["hab_left"][:o.n_hab_left]}
+    r = {"status": status, "found": bool(o.found), "n_nodes": o.n_nodes, "n_expansions": o.n_expansions,
+         "n_children": o.n_children, "visited_count": o.visited_count,
+         "expansions": a["exp_log"][:o.n_expansions], "path": a["path"][:o.path_len],
+         "cost_list": a["cost_list"][:o.path_len], "node_path": a["node_path"][:o.path_len],
+         "smooth_path": a["smooth_path"][:o.smooth_len], "hab_left": a["hab_left"][:o.n_hab_left]}
+    if vis_out is not None:
+        r["visited"] = vis_out
+    return r

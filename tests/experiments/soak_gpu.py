@@ -4,7 +4,9 @@ Every case draws a world and planner parameters at random and compares, bit for 
 kernel, the one-episode kernel and the CPU checker (RRT.exploring, time-bin sampling; nearest-neighbour -- scan and fallback --
 and plan-time sampling), the astar_fixLenSOG / astar_fixLen searches and Planner_RRT.planning (latency, throughput and
 four-episodes-per-wavefront kernels) with the checker.  The four-episode kernel runs at a drawn workgroup size (option
-ROWS_WG_WAVES: unset, 1, 2, 5, 7 or 12 waves).  Prints one line per failure and a summary; exit code 1 on any mismatch."""
+ROWS_WG_WAVES: unset, 1, 2, 5, 7 or 12 waves), Planner_RRT's at a drawn cap of its workgroups (option PRRT_ROWS_GRID: unset, 1
+or 3; with a cap the batch is repeated until it has more episodes than rows, so that rows take further episodes from the work
+counter).  Prints one line per failure and a summary; exit code 1 on any mismatch."""
 import os
 import random
 import sys
@@ -21,6 +23,7 @@ from oracle import orc, orc_astar as oa, orc_planner as op  # noqa: E402
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+grid_rng = random.Random("prrt rows grid %d" % (int(sys.argv[2]) if len(sys.argv) > 2 else 1))  # (its own stream: the cases stay what they were)
 BIG = len(sys.argv) > 3 and sys.argv[3] == "big"  # fewer, longer RRT episodes (member-list chunks, thousands of leaves)
 ctx = _lib.Context(0)
 fails = 0
@@ -167,19 +170,30 @@ def planner_case(i):
     goals[1] = [w["start"][0] + rng.uniform(3, 12), w["start"][1] + rng.uniform(-3, 3)]  # a goal that is reached early
     # the one-episode kernel (latency and throughput instantiations) and, where its limits allow, four episodes per wavefront
     variants = [("lat", {"AUVP_PRRT_ROWS": "0", "AUVP_PRRT_LAT": "1"}), ("thr", {"AUVP_PRRT_ROWS": "0", "AUVP_PRRT_LAT": "0"})]
+    # ... at a drawn cap of its workgroups (option PRRT_ROWS_GRID; None: the host's grid).  With a cap the batch is repeated 13
+    # times: 52 episodes on 16 or 48 rows, so every row or some take a second episode from the work counter (episode e = e % 4)
+    rows_grid = grid_rng.choice([None, 1, 3])
     if freq <= 15 and len(w["obstacles"]) <= 256:
-        variants.append(("rows", {"AUVP_PRRT_ROWS": "1", "AUVP_PRRT_LAT": "0"}))
+        env = {"AUVP_PRRT_ROWS": "1", "AUVP_PRRT_LAT": "0"}
+        if rows_grid is not None:
+            env["AUVP_PRRT_ROWS_GRID"] = str(rows_grid)
+        variants.append(("rows" if rows_grid is None else "rows, at most %d workgroups" % rows_grid, env))
     ref = [op.planning(w["obstacles"], w["rect"], starts[e], goals[e], int(seeds[e]), max_step, freq=freq, cell=cell, subs=subs,
                        kind="portable") for e in range(n_ep)]
     for name, env in variants:
+        reps = 13 if "AUVP_PRRT_ROWS_GRID" in env else 1
         os.environ.update(env)
-        pb = PlannerBatch(ctx, starts, goals, w["rect"], max_step, seeds=seeds, freq=freq, cell=cell, subs=subs)
+        pb = PlannerBatch(ctx, np.tile(starts, (reps, 1)), np.tile(goals, (reps, 1)), w["rect"], max_step, seeds=np.tile(seeds, reps),
+                          freq=freq, cell=cell, subs=subs)
         s = pb.plan()
-        trees = [pb.tree(e, s[e]) for e in range(n_ep)]
+        if reps > 1 and not (ctx.prrt_last_kernel() == "prrt_rows_kernel" and ctx.last_launch()[0] * 16 < n_ep * reps):
+            fails += 1
+            print("PLANNER case", i, name, "did not run on fewer rows than episodes:", ctx.prrt_last_kernel(), ctx.last_launch())
+        trees = [pb.tree(e, s[e]) for e in range(n_ep * reps)]
         for k in env:
             os.environ.pop(k)
-        for e in range(n_ep):
-            r = ref[e]
+        for e in range(n_ep * reps):
+            r = ref[e % n_ep]
             st = {-1: -2, -2: -1}.get(int(s["status"][e]), int(s["status"][e]))  # (the two sides number ARG / CAPACITY differently)
             ok = (st, int(s["n_nodes"][e]), int(s["steps"][e]), bool(s["done"][e])) == \
                  (r["status"], r["n_nodes"], r["steps"], r["done"]) and float(s["rng_after"][e]) == r["rng_after"]

@@ -176,14 +176,17 @@ def test_stand_in_agent_is_a_pure_function_of_seed_environment_and_step_count():
     assert still.sum() >= 4 and not np.array_equal(b[still], c[still])
 
 
-@pytest.mark.parametrize("rows", [False, True])
-def test_env_device_loop_as_a_graph_equals_eager(rows, monkeypatch):
-    """one step of the device-resident loop (stand-in agent + generate_one_node + observation + outcome) captured as a
-    hipGraph and replayed n times == the same n steps enqueued one by one: the loop's step counter lives in HBM, so every
-    replay draws anew.  rows: the four-episodes-per-wavefront kernel (AUVP_PRRT_ROWS=1; the default of large batches), whose
-    work counter must restart at every replay (a memset node) -- and eager steps AFTER the replays must still be right"""
+_LOOP_EAGER = {}  # the eager run of the loop below by kernel choice: the one-episode kernel's is the reference of the others
+
+
+def _device_loop_runs(rows, monkeypatch, graphs=(False, True)):
+    """the loop of test_env_device_loop_as_a_graph_equals_eager, enqueued step by step / captured and replayed"""
+    for k in ("AUVP_PRRT_ROWS", "AUVP_PRRT_ROWS_GRID"):
+        monkeypatch.delenv(k, raising=False)
     if rows:
         monkeypatch.setenv("AUVP_PRRT_ROWS", "1")
+    if rows == "one_workgroup":
+        monkeypatch.setenv("AUVP_PRRT_ROWS_GRID", "1")
     from auv_sim_amd import synth
     from auv_sim_amd.motion_plan_state import Motion_plan_state as MPS
     from auv_sim_amd.rrt_env import RRTEnvBatch
@@ -193,7 +196,7 @@ def test_env_device_loop_as_a_graph_equals_eager(rows, monkeypatch):
     auv, shark = MPS(float(w["start"][0]), float(w["start"][1]), z=-5.0), MPS(float(w["goal"][0]), float(w["goal"][1]), z=-5.0)
     E, n_steps = 40, 90
     out = []
-    for graph in (False, True):
+    for graph in graphs:
         env = RRTEnvBatch(auv, shark, bnd, 5, 1, obstacles, seeds=list(range(E)), max_nodes=n_steps + 8, freq=10)
         env.reset()
         d = env.device_buffers()
@@ -204,6 +207,8 @@ def test_env_device_loop_as_a_graph_equals_eager(rows, monkeypatch):
         one_step()  # first-use allocations; also step 0 of both runs
         if rows:
             assert env._ctx.prrt_last_kernel() == "prrt_rows_kernel"
+            # 40 environments: three workgroups of 16 rows by default; on one, every launch and every replay refills its rows
+            assert env._ctx.last_launch()[:2] == ((1 if rows == "one_workgroup" else 3), 256)
         if graph:
             gid = env.capture_step(one_step)
             env.replay(gid, n_steps - 1 - 6)
@@ -217,10 +222,32 @@ def test_env_device_loop_as_a_graph_equals_eager(rows, monkeypatch):
         env.sync()
         out.append((d["num_nodes"].cpu().numpy().copy(), d["reward"].cpu().numpy().copy(), d["done"].cpu().numpy().copy(),
                     [env.tree(e)["nodes"] for e in (0, E - 1)]))
-    a, b = out
+        if not graph:
+            _LOOP_EAGER[rows] = out[-1]
+    return out
+
+
+@pytest.mark.parametrize("rows", [False, True, "one_workgroup"])
+def test_env_device_loop_as_a_graph_equals_eager(rows, monkeypatch):
+    """one step of the device-resident loop (stand-in agent + generate_one_node + observation + outcome) captured as a
+    hipGraph and replayed n times == the same n steps enqueued one by one: the loop's step counter lives in HBM, so every
+    replay draws anew.  rows: the four-episodes-per-wavefront kernel (AUVP_PRRT_ROWS=1; the default of large batches), whose
+    work counter must restart at every replay (a memset node) -- and eager steps AFTER the replays must still be right.
+    "one_workgroup": that kernel on 16 rows for the 40 environments (AUVP_PRRT_ROWS_GRID=1), so that every replay hands rows a
+    second and a third environment behind the memset node.  Whatever the kernel, the loop computes what the one-episode kernel's
+    eager loop does."""
+    E = 40
+    a, b = _device_loop_runs(rows, monkeypatch)
     assert a[0].sum() > E * 5  # trees grew
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
     assert all(np.array_equal(x, y) for x, y in zip(a[3], b[3]))
+    if rows:
+        if False not in _LOOP_EAGER:
+            _device_loop_runs(False, monkeypatch, graphs=(False,))
+        ref = _LOOP_EAGER[False]
+        for got in (a, b):
+            assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2])
+            assert all(np.array_equal(x, y) for x, y in zip(got[3], ref[3]))
 
 
 def _small_env(E=16, max_nodes=100, seeds=None):

@@ -353,6 +353,37 @@ def test_prrt_options():
     assert (big["next_lds"], big["bk_lds"]) == (1, 0)
 
 
+def test_prrt_rows_grid_option_only_lowers_the_grid():
+    """PRRT_ROWS_GRID: at most that many workgroups for prrt_rows_kernel, at least one (tests: fewer rows than episodes, so that
+    every batch refills its rows from the work counter); nothing else of the plan moves, and the other kernels ignore it"""
+    full, small = prrt(16384), prrt(3073)
+    assert (full["grid"], small["grid"]) == (768, 193)
+    p = prrt(16384, options=dict(PRRT_ROWS_GRID=2))
+    assert p["grid"] == 2 and {k: v for k, v in p.items() if k != "grid"} == {k: v for k, v in full.items() if k != "grid"}
+    assert prrt(3073, options=dict(PRRT_ROWS_GRID=192))["grid"] == 192
+    # a cap at or above the default leaves it
+    for cap in (768, 769, 100000, 1 << 40):
+        assert prrt(16384, options=dict(PRRT_ROWS_GRID=cap)) == full
+    for cap in (193, 194, 768):
+        assert prrt(3073, options=dict(PRRT_ROWS_GRID=cap)) == small
+    # below 1 counts as 1
+    for cap in (1, 0, -3):
+        assert prrt(16384, options=dict(PRRT_ROWS_GRID=cap))["grid"] == 1
+        assert prrt(3073, options=dict(PRRT_ROWS_GRID=cap))["grid"] == 1
+    # forced rows batches, step mode and enqueue-only launches: the same rule
+    assert prrt(130, options=dict(PRRT_ROWS=1, PRRT_LAT=0))["grid"] == 9
+    assert prrt(130, options=dict(PRRT_ROWS=1, PRRT_LAT=0, PRRT_ROWS_GRID=2))["grid"] == 2
+    assert prrt(45, rows=True, step_mode=1, options=dict(PRRT_ROWS_GRID=1))["grid"] == 1
+    assert prrt(40, rows=True, step_mode=1, waits=False, options=dict(PRRT_ROWS_GRID=1))["grid"] == 1
+    assert prrt(100000, n_cu=304, options=dict(PRRT_ROWS_GRID=5000))["grid"] == 3 * 304
+    # prrt_kernel / prrt_pipe_kernel plans do not read it
+    for E in (512, 769, 1025, 3072):
+        for cap in (1, 0, 2):
+            assert prrt(E, options=dict(PRRT_ROWS_GRID=cap)) == prrt(E), (E, cap)
+    assert prrt(4096, options=dict(PRRT_ROWS=0, PRRT_ROWS_GRID=1)) == prrt(4096, options=dict(PRRT_ROWS=0))
+    assert "PRRT_ROWS_GRID" in _lib.OPTION_NAMES
+
+
 def test_prrt_thresholds_follow_the_cu_count():
     assert prrt(12 * 304, n_cu=304)["name"] == "prrt_kernel" and prrt(12 * 304 + 1, n_cu=304)["name"] == "prrt_rows_kernel"
     assert prrt(4 * 304, n_cu=304)["name"] == "prrt_pipe_kernel" and prrt(4 * 304 + 1, n_cu=304)["name"] == "prrt_kernel"
