@@ -43,6 +43,18 @@ SUMMARY_DTYPE = np.dtype([("status", "<i4"), ("n_nodes", "<i4"), ("n_points", "<
                           ("nn_scanned", "<u8")])
 assert SUMMARY_DTYPE.itemsize == C.sizeof(RRTSummary)
 
+
+
+class RRTGroupBest(C.Structure):
+    """struct auvp_rrt_group_best (include/auvplan.h): the winner of one group of episodes"""
+    _fields_ = [("status", C.c_int32), ("winner", C.c_int32), ("n_with_leaf", C.c_int32), ("path_len", C.c_int32),
+                ("cost", C.c_double * 4), ("length", C.c_double)]
+
+
+GROUP_BEST_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_with_leaf", "<i4"), ("path_len", "<i4"),
+                             ("cost", "<f8", (4,)), ("length", "<f8")])
+assert GROUP_BEST_DTYPE.itemsize == C.sizeof(RRTGroupBest)
+
 MODES = {"timebin": 0, "plantime": 1, "nn": 2}
 # auvp_rrt_episode (include/auvplan.h): one episode's own horizon and habitat list (bit h = habitat h of the world's table)
 EPISODE_DTYPE = np.dtype([("max_traj_time", "<f8"), ("habitat_keep", "<u8")])
@@ -109,6 +121,12 @@ def load():
     L.auvp_rrt_bin_sizes.argtypes = [vp, C.c_int32, _ip, _ip]
     L.auvp_rrt_summaries_dev.argtypes = [vp]
     L.auvp_rrt_summaries_dev.restype = C.c_void_p
+    if hasattr(L, "auvp_rrt_group_best"):  # (as below: an earlier build loaded for a comparison has none of them)
+        L.auvp_rrt_group_best.argtypes = [vp, C.c_int32, _ip, C.c_void_p]
+        L.auvp_rrt_group_best_dev.argtypes = [vp]
+        L.auvp_rrt_group_best_dev.restype = C.c_void_p
+        L.auvp_rrt_group_paths.argtypes = [vp, C.POINTER(C.c_int64), _dp]
+        L.auvp_rrt_group_paths_dev.argtypes = [vp, C.POINTER(C.c_int64), C.c_void_p]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -343,11 +361,12 @@ class Context:
     def rrt_explore_batch(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,
                           max_traj_time=500.0, weights=(-3, -3, -4), dist_to_end=2, diff_max=0.5, min_dist=0.5,
                           max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False,
-                          habitat_keep=None):
+                          habitat_keep=None, summaries=True):
+        """prepare + run; the summaries, or None with summaries=False (they stay in HBM: rrt_group_best reads them there)"""
         self.rrt_prepare(init, seeds, n_iter, mode, freq, bin_interval, v, max_traj_time, weights, dist_to_end,
                          diff_max, min_dist, max_plan_time, points_per_iter, iter_log, leaf_log, phase_clocks, habitat_keep)
         self.rrt_run()
-        return self.summaries()
+        return self.summaries() if summaries else None
 
     def rrt_run(self):
         """launch the kernel on the prepared batch (inputs already resident in HBM); repeatable"""
@@ -411,6 +430,43 @@ class Context:
         data_ptr()) -- stays in HBM for the multi-GPU gather"""
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         self._chk(self.L.auvp_rrt_paths_dev(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(out_dev_ptr)))
+
+    # ---- best-of-K: the winner of every group of episodes, chosen on the device ----
+    def rrt_group_best(self, group_off):
+        """winner of every group of the batch that just ran (auvp_rrt_group_best): group g = episodes group_off[g] ..
+        group_off[g+1]-1, the groups partition the batch.  Returns [G] GROUP_BEST_DTYPE records: status (0, NO_QUALIFYING_LEAF,
+        or the status < 0 of the lowest-indexed failed member), winner (episode index or -1), n_with_leaf, and the winner's
+        path_len, cost [4], length."""
+        off = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+        G = len(off) - 1
+        out = np.zeros(max(G, 1), dtype=GROUP_BEST_DTYPE)
+        self._chk(self.L.auvp_rrt_group_best(self.h, G, _p(off, _ip), out.ctypes.data_as(C.c_void_p)))
+        return out[:G]
+
+    def group_best_dev(self):
+        """device pointer of the last rrt_group_best call's records (None: none since the batch ran)"""
+        return self.L.auvp_rrt_group_best_dev(self.h)
+
+    @staticmethod
+    def group_offsets(best):
+        """[G+1] row offsets of the winners' courses: the exclusive prefix sum of path_len (0 without a winner)"""
+        lens = np.where(best["winner"] >= 0, best["path_len"], 0).astype(np.int64)
+        off = np.zeros(len(best) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        return off
+
+    def group_paths(self, best):
+        """final course (root -> leaf) of every group's winner: list of [L,7] arrays, empty where there is none.  Only these
+        rows are copied to the host."""
+        off = self.group_offsets(best)
+        out = np.zeros((max(int(off[-1]), 1), 7))
+        self._chk(self.L.auvp_rrt_group_paths(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), _p(out)))
+        return [out[off[g]:off[g + 1]] for g in range(len(best))]
+
+    def group_paths_dev(self, offsets, out_dev_ptr):
+        """the winners' courses written to a caller-owned device buffer [offsets[G],7] f64"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        self._chk(self.L.auvp_rrt_group_paths_dev(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(out_dev_ptr)))
 
     def tree(self, ep, summary):
         n, npnt = int(summary["n_nodes"]), int(summary["n_points"])

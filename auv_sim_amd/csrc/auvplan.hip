@@ -18,6 +18,7 @@
 #include "../../include/auvplan.h"
 #include "auvp_seed.h"
 #include "rrt_explore_kernel.h"
+#include "rrt_group_kernel.h"
 #include "rrt_rows_kernel.h"
 #include "rrt_rows_stream_kernel.h"  // (the LDS plan; the kernel itself is launched from rows_kernels.hip)
 #include "rrt_duo_kernel.h"
@@ -38,6 +39,7 @@ extern "C" hipError_t auvpi_rrt_rows_launch(const auvp::WorldDev* W, const auvp:
                                             int grid, int block, int lds_max, int lds, hipStream_t stream);
 
 static_assert(sizeof(auvp_rrt_summary) == sizeof(RrtSummary), "summary layout");
+static_assert(sizeof(struct auvp_rrt_group_best) == sizeof(RrtGroupBest), "group record layout");
 
 namespace {
 
@@ -97,6 +99,11 @@ struct auvp_handle {
   DevBuf d_nodes_f, d_nodes_i, d_points, d_bin_items, d_bin_count, d_mt, d_mtidx, d_seeds, d_init, d_summary, d_itlog_i, d_itlog_b,
       d_leaf_c, d_leaf_i, d_phase, d_leaf_stats, d_node_c, d_node_q, d_node_xy, d_tmp0, d_tmp1, d_tmp2, d_tmp3, d_tmp4, d_tmp5, d_stream;
   bool have_batch = false, prepared = false;
+  // best-of-K selection (auvp_rrt_group_best) of the batch that ran last: the records in HBM and their host copy (the offsets
+  // of auvp_rrt_group_paths are checked against it before anything is written)
+  DevBuf d_group_off, d_group_best, d_group_pos;
+  std::vector<RrtGroupBest> group_best;
+  bool have_group = false;
   // per-episode limits (auvp_rrt_prepare_episodes): the batch runs rrt_explore_lim_kernel + rrt_leaf_lim_kernel; lim_K: every
   // episode's own K (P.K is the cap's)
   bool lim = false;
@@ -828,6 +835,7 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
   h->E = E;
   h->prepared = true;
   h->have_batch = false;
+  h->have_group = false;
   return AUVP_OK;
 }
 
@@ -1036,6 +1044,7 @@ int auvp_rrt_run(auvp_handle* h) {
   if (!h) return AUVP_ERR_ARG;
   if (!h->prepared) return fail(h, AUVP_ERR_STATE, "auvp_rrt_prepare not called");
   HIPCHK(h, hipSetDevice(h->device));
+  h->have_group = false;
   h->pipe_clear();
   h->pipe_fallback_last = 0;
   int rc = rrt_run_pass(h, false);
@@ -1088,6 +1097,69 @@ int auvp_rrt_paths(auvp_handle* h, const int64_t* offsets, double* out) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, h->d_tmp1.reserve(std::max<size_t>(total, 1) * 7 * sizeof(double)));
   int rc = auvp_rrt_paths_dev(h, offsets, h->d_tmp1.p);
+  if (rc != AUVP_OK) return rc;
+  if (total) HIPCHK(h, hipMemcpyAsync(out, h->d_tmp1.p, total * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return AUVP_OK;
+}
+
+int auvp_rrt_group_best(auvp_handle* h, int32_t G, const int32_t* group_off, struct auvp_rrt_group_best* out) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!h->have_batch) return fail(h, AUVP_ERR_STATE, "no batch has run");
+  if (G < 1 || !group_off) return fail(h, AUVP_ERR_ARG, "bad group arguments");
+  const int E = h->E;
+  if (G > E || group_off[0] != 0 || group_off[G] != E) return fail(h, AUVP_ERR_ARG, "the groups do not partition the batch of %d", E);
+  for (int g = 0; g < G; g++)
+    if (group_off[g + 1] <= group_off[g]) return fail(h, AUVP_ERR_ARG, "group %d is empty or out of order", g);
+  HIPCHK(h, hipSetDevice(h->device));
+  h->have_group = false;
+  int rc = upload(h, h->d_group_off, group_off, (size_t)G + 1);
+  if (rc != AUVP_OK) return rc;
+  HIPCHK(h, h->d_group_best.reserve((size_t)G * sizeof(RrtGroupBest)));
+  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0,
+                     h->stream, h->B.summary, h->d_group_off.as<int32_t>(), h->d_group_best.as<RrtGroupBest>(), (int)G);
+  HIPCHK(h, hipGetLastError());
+  h->group_best.resize((size_t)G);
+  HIPCHK(h, hipMemcpyAsync(h->group_best.data(), h->d_group_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (out) memcpy(out, h->group_best.data(), (size_t)G * sizeof(RrtGroupBest));
+  h->have_group = true;
+  return AUVP_OK;
+}
+
+void* auvp_rrt_group_best_dev(auvp_handle* h) { return (h && h->have_batch && h->have_group) ? h->d_group_best.p : nullptr; }
+
+int auvp_rrt_group_paths_dev(auvp_handle* h, const int64_t* offsets, void* out_dev) {
+  if (!h || !offsets || !out_dev) return AUVP_ERR_ARG;
+  if (!h->have_batch) return fail(h, AUVP_ERR_STATE, "no batch has run");
+  if (!h->have_group) return fail(h, AUVP_ERR_STATE, "auvp_rrt_group_best not called for this batch");
+  const int G = (int)h->group_best.size();
+  if (offsets[0] < 0) return fail(h, AUVP_ERR_ARG, "offsets[0] < 0");
+  for (int g = 0; g < G; g++) {
+    const RrtGroupBest& r = h->group_best[(size_t)g];
+    const int64_t need = r.winner >= 0 ? (int64_t)r.path_len : 0;
+    if (offsets[g + 1] - offsets[g] < need) return fail(h, AUVP_ERR_ARG, "group %d: the offsets leave fewer rows than its course of %lld", g, (long long)need);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = upload(h, h->d_group_pos, offsets, (size_t)G + 1);
+  if (rc != AUVP_OK) return rc;
+  hipLaunchKernelGGL(rrt_group_course_kernel, dim3(G), dim3(64), 0, h->stream, h->B, h->d_group_best.as<RrtGroupBest>(),
+                     h->d_group_pos.as<int64_t>(), reinterpret_cast<double*>(out_dev), G, h->E);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return AUVP_OK;
+}
+
+int auvp_rrt_group_paths(auvp_handle* h, const int64_t* offsets, double* out) {
+  if (!h || !offsets || !out) return AUVP_ERR_ARG;
+  if (!h->have_batch) return fail(h, AUVP_ERR_STATE, "no batch has run");
+  if (!h->have_group) return fail(h, AUVP_ERR_STATE, "auvp_rrt_group_best not called for this batch");
+  const int64_t last = offsets[h->group_best.size()];
+  if (last < 0) return fail(h, AUVP_ERR_ARG, "negative offsets");
+  const size_t total = (size_t)last;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, h->d_tmp1.reserve(std::max<size_t>(total, 1) * 7 * sizeof(double)));
+  int rc = auvp_rrt_group_paths_dev(h, offsets, h->d_tmp1.p);
   if (rc != AUVP_OK) return rc;
   if (total) HIPCHK(h, hipMemcpyAsync(out, h->d_tmp1.p, total * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

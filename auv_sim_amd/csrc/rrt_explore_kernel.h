@@ -593,11 +593,9 @@ static __global__ __launch_bounds__(RRT_LEAF_WAVES * 64) __attribute__((amdgpu_w
 #include "rrt_leaf_body.h"
 }
 
-// generate_final_course (:321-331) of the best leaf, written root -> leaf (exploring reverses it, :174)
-static __global__ __launch_bounds__(64) void rrt_final_course_kernel(RrtBuffers B, const int64_t* __restrict__ offsets,
-                                                              double* __restrict__ out, int n_episodes) {
-  const int ep = blockIdx.x;
-  if (ep >= n_episodes) return;
+// generate_final_course (:321-331) of episode ep's best leaf, written root -> leaf (exploring reverses it, :174) from o on: one
+// wavefront walks leaf -> root and fills the elements from the back (nothing is written for an episode without a leaf)
+__device__ inline void rrt_final_course(const RrtBuffers& B, int ep, double* __restrict__ o) {
   const int lane = lane_id();
   const RrtSummary s = B.summary[ep];
   if (s.best_leaf < 0) return;
@@ -607,7 +605,6 @@ static __global__ __launch_bounds__(64) void rrt_final_course_kernel(RrtBuffers 
   const int4* nodeI = reinterpret_cast<const int4*>(B.node_i) + (size_t)ep * capn;
   const double* ptF = B.points + (size_t)ep * capp * 6;
   const double* init = B.init + (size_t)ep * 6;
-  double* o = out + 7 * (size_t)offsets[ep];
   int pos = s.best_path_len - 1;  // element index of the leaf
   auto node_elem = [&](int m, int at) {
     double* e = o + 7 * (size_t)at;
@@ -639,6 +636,14 @@ static __global__ __launch_bounds__(64) void rrt_final_course_kernel(RrtBuffers 
     pos--;
     m = r.y;
   }
+}
+
+// ... of every episode of the batch, at offsets[ep]
+static __global__ __launch_bounds__(64) void rrt_final_course_kernel(RrtBuffers B, const int64_t* __restrict__ offsets,
+                                                              double* __restrict__ out, int n_episodes) {
+  const int ep = blockIdx.x;
+  if (ep >= n_episodes) return;
+  rrt_final_course(B, ep, out + 7 * (size_t)offsets[ep]);
 }
 
 }  // namespace auvp

@@ -202,8 +202,9 @@ class RRT:
         return out
 
     def _explore_summaries(self, initials, habitats, bin_interval, v, traj_time_stamp, max_traj_time, plan_time, weights,
-                           max_iter, seed_arg, habitat_masks=None):
-        """one prepare + run of exploring episodes on this object's context; the summaries (statuses unchecked)"""
+                           max_iter, seed_arg, habitat_masks=None, summaries=True):
+        """one prepare + run of exploring episodes on this object's context; the summaries (statuses unchecked), or None with
+        summaries=False: they stay in HBM (best-of-K planning reads them there)"""
         mode = "timebin" if (plan_time and traj_time_stamp) else ("plantime" if plan_time else "nn")
         hab = _circles(habitats)
         self._ctx.set_habitats(hab)
@@ -216,7 +217,55 @@ class RRT:
                                            bin_interval=bin_interval, v=v, max_traj_time=max_traj_time,
                                            weights=weights, dist_to_end=self.dist_to_end, diff_max=self.diff_max,
                                            min_dist=0.5, max_plan_time=float(max_iter),  # virtual clock: 1 tick per iteration
-                                           habitat_keep=keep)
+                                           habitat_keep=keep, **({} if summaries else {"summaries": False}))
+
+    def exploring_best_of(self, initials, habitats, plot_interval, bin_interval, v, shark_interval, traj_time_stamp=False,
+                          max_plan_time=5, max_traj_time=200.0, plan_time=True, weights=[-1, -1, -1], max_iter=None,
+                          seeds=None, habitat_masks=None):
+        """Best of K trees for each of N AUVs in one launch: seeds [N][K]; AUV i's members are the batch's episodes i*K ..
+        i*K+K-1, each an ordinary exploring episode from initials[i] with seeds[i][m] (and max_traj_time[i], habitat_masks[i]
+        where those are per AUV, as in exploring_batch).  The winner is exploring's own rule folded over the members in order
+        (the lowest cost, the earliest member among equal costs), chosen on the device; only the winners' courses are copied to
+        the host and turned into objects.  Returns N dicts shaped like exploring's plus "tree", the winning member's index;
+        None where no member has a qualifying leaf.  A member that failed on the device raises AuvpError."""
+        N = len(initials)
+        if seeds is None or len(seeds) != N or N == 0:
+            raise ValueError("seeds [N][K] are required: one row of K seeds per AUV")
+        K = len(seeds[0])
+        if K < 1 or any(len(row) != K for row in seeds):
+            raise ValueError("every AUV needs the same number (>= 1) of seeds")
+        if max_iter is None:
+            max_iter = max(1, int(math.ceil(max_plan_time * self.iters_per_second)))
+        seed_arg = np.array([int(s) for row in seeds for s in row], dtype=np.uint64)
+        members = [initials[i] for i in range(N) for _ in range(K)]
+        per_auv = habitat_masks is not None or np.ndim(max_traj_time) > 0
+        horizons = np.broadcast_to(np.asarray(max_traj_time, dtype=np.float64), (N,))
+        mtt = np.repeat(horizons, K) if per_auv else max_traj_time
+        masks = np.repeat(np.array(habitat_keep_bits(habitat_masks, len(habitats), N), dtype=object), K).tolist() if per_auv else None
+        self._explore_summaries(members, habitats, bin_interval, v, traj_time_stamp, mtt, plan_time, weights, max_iter,
+                                seed_arg, masks, summaries=False)
+        best = self._ctx.rrt_group_best(np.arange(N + 1, dtype=np.int64) * K)
+        bad = best["status"] < 0
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise _lib.AuvpError(int(best[i]["status"]), "a tree of AUV %d failed on the device (status %d)" % (i, int(best[i]["status"])))
+        paths = self._ctx.group_paths(best)
+        self._last = None  # (mps_list is the tree of a single exploring call)
+        self._mps_cache = None
+        self.t_start = 0.0
+        out = []
+        for i in range(N):
+            b = best[i]
+            if b["winner"] < 0:
+                out.append(None)
+                continue
+            course = self._materialise_course(paths[i], initials[i])
+            h = max_traj_time if np.ndim(max_traj_time) == 0 else float(horizons[i])
+            split = self.splitPath(course, shark_interval, [initials[i].traj_time_stamp, h])
+            c = [float(x) for x in b["cost"]]
+            out.append({"path length": float(b["length"]), "path": [course, split], "cost": [c[0], c[1:]],
+                        "tree": int(b["winner"]) - i * K})
+        return out
 
     def replanning(self, start, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
                    max_iter=None, seed=None):
@@ -258,7 +307,7 @@ class RRT:
         return [committed[1:], rounds, total]
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
-                         max_iter=None, seeds=None, rngs=None, as_arrays=False):
+                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1):
         """N independent replanning() loops, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
@@ -269,9 +318,20 @@ class RRT:
         Returns a list of [committed trajectory, {round: [bucket, habitats at that round]}, cost, habitats left]
         (Motion_plan_state objects and the caller's habitat objects; the first three as replanning returns them) or, with as_arrays=True, of dicts of numpy arrays: traj [n,7] (x, y, theta, v, traj_time_stamp,
         plan_time_stamp, length), round_len [R], round_keep [R] (habitat bit masks at each round), round_max_traj_time [R],
-        round_cost [R,4], keep (the habitats left), cost [4].  The SharkUpdate that replanning leaves in self.sharkEstimate
-        is not built (nothing reads it)."""
+        round_cost [R,4], round_tree [R], keep (the habitats left), cost [4].  The SharkUpdate that replanning leaves in
+        self.sharkEstimate is not built (nothing reads it).
+
+        trees_per_auv = K > 1: every round grows K trees per AUV -- AUV e draws K seeds from its stream in member order, all K
+        plan from its committed state with its horizon and habitat list -- and commits the first bucket of the best one (the
+        rule of exploring_best_of, chosen on the device; only the winners' courses reach the host).  round_tree names the
+        winning member of each round.  An AUV without a winner in some round gets None.  Seeds only: one generator cannot
+        continue K streams, so rngs raises ValueError."""
         N = len(starts)
+        K = int(trees_per_auv)
+        if K < 1:
+            raise ValueError("trees_per_auv must be >= 1")
+        if K > 1 and rngs is not None:
+            raise ValueError("rngs cannot be combined with trees_per_auv > 1: one generator cannot continue K streams")
         horizon_end = list(self.sharkGrid.keys())[-1][1]
         round_span = plan_time_budget + replan_time_interval
         all_habitats = list(habitats)
@@ -304,27 +364,14 @@ class RRT:
                 if ttl[e] + last[e][4] > horizon_end:  # stays clipped for the later rounds too (:76-77)
                     ttl[e] = horizon_end - last[e][4]
             mtt = np.array([ttl[e] + last[e][4] for e in act], dtype=np.float64)
-            round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
-            if all(gens[e] is None for e in act):
-                seed_arg = np.array([round_seeds[e] for e in act], dtype=np.uint64)
+            if K > 1:
+                status, best_cost, tree, paths = self._replan_round_best_of(act, K, streams, last, all_habitats, mtt, keep, weight,
+                                                                            max_iter)
             else:
-                st = [_mt_state_of(gens[e].getstate() if gens[e] is not None else random.Random(round_seeds[e]).getstate())
-                      for e in act]
-                seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
-            init_objs = [_Init(last[e]) for e in act]
-            summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, mtt, True, weight, max_iter, seed_arg,
-                                           [keep[e] for e in act])
+                status, best_cost, tree, paths = self._replan_round(act, streams, gens, last, all_habitats, mtt, keep, weight,
+                                                                    max_iter)
             for i, e in enumerate(act):
-                n = int(summ[i]["n_draw32"])
-                if gens[e] is not None and n:
-                    gens[e].getrandbits(32 * n)  # what exploring does to the global stream
-            bad = summ["status"] < 0
-            if bad.any():
-                i = int(np.argmax(bad))
-                raise _lib.AuvpError(int(summ[i]["status"]), "AUV %d failed on the device (status %d)" % (act[i], int(summ[i]["status"])))
-            paths = self._ctx.paths(summ)
-            for i, e in enumerate(act):
-                if summ[i]["status"] == _lib.NO_QUALIFYING_LEAF:
+                if status[i] == _lib.NO_QUALIFYING_LEAF:
                     alive[e] = False
                     traj[e] = None
                     continue
@@ -334,7 +381,7 @@ class RRT:
                 bucket = p[sel]
                 if as_arrays:
                     traj[e].append(bucket)
-                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(summ[i]["best_cost"])))
+                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(best_cost[i]), int(tree[i])))
                 else:
                     course = self._materialise_course(paths[i], last_obj[e])
                     objs = [course[j] for j in np.flatnonzero(sel)]
@@ -368,13 +415,52 @@ class RRT:
                 res.append(dict(traj=rows[e], round_len=np.array([x[0] for x in r], dtype=np.int64),
                                 round_keep=np.array([x[1] for x in r], dtype=np.uint64),
                                 round_max_traj_time=np.array([x[2] for x in r]),
-                                round_cost=np.array([x[3] for x in r]).reshape(-1, 4), keep=keep[e], cost=costs[e]))
+                                round_cost=np.array([x[3] for x in r]).reshape(-1, 4),
+                                round_tree=np.array([x[4] for x in r], dtype=np.int64), keep=keep[e], cost=costs[e]))
             else:
                 c = costs[e]
                 res.append([traj[e], {k + 1: [b, hl] for k, (b, hl) in enumerate(rounds[e])},
                             [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
                             [all_habitats[h] for h in range(H) if (keep[e] >> h) & 1]])
         return res
+
+    def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter):
+        """one round of replanning_batch, one tree per active AUV: (status [A], best_cost [A,4], tree [A] = 0, courses)"""
+        round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
+        if all(gens[e] is None for e in act):
+            seed_arg = np.array([round_seeds[e] for e in act], dtype=np.uint64)
+        else:
+            st = [_mt_state_of(gens[e].getstate() if gens[e] is not None else random.Random(round_seeds[e]).getstate())
+                  for e in act]
+            seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
+        init_objs = [_Init(last[e]) for e in act]
+        summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, mtt, True, weight, max_iter, seed_arg,
+                                       [keep[e] for e in act])
+        for i, e in enumerate(act):
+            n = int(summ[i]["n_draw32"])
+            if gens[e] is not None and n:
+                gens[e].getrandbits(32 * n)  # what exploring does to the global stream
+        bad = summ["status"] < 0
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise _lib.AuvpError(int(summ[i]["status"]), "AUV %d failed on the device (status %d)" % (act[i], int(summ[i]["status"])))
+        paths = self._ctx.paths(summ)
+        return summ["status"], summ["best_cost"], np.zeros(len(act), dtype=np.int64), paths
+
+    def _replan_round_best_of(self, act, K, streams, last, all_habitats, mtt, keep, weight, max_iter):
+        """one round with K trees per active AUV: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s members; the winners are
+        chosen on the device and only their courses are copied.  Returns as _replan_round, tree = the winning member."""
+        seed_arg = np.array([streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
+        init_objs = [_Init(last[e]) for e in act for _ in range(K)]
+        self._explore_summaries(init_objs, all_habitats, 5, 2, True, np.repeat(mtt, K), True, weight, max_iter, seed_arg,
+                                [keep[e] for e in act for _ in range(K)], summaries=False)
+        best = self._ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
+        bad = best["status"] < 0
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise _lib.AuvpError(int(best[i]["status"]), "a tree of AUV %d failed on the device (status %d)" % (act[i], int(best[i]["status"])))
+        tree = np.where(best["winner"] >= 0, best["winner"] - np.arange(len(act)) * K, -1)
+        return best["status"], best["cost"], tree, self._ctx.group_paths(best)
 
     # ------------------------------------------------------------------ host-side helpers (reference names)
     def splitPath(self, path, shark_interval, traj_time):

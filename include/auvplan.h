@@ -151,6 +151,35 @@ int auvp_rrt_bin_sizes(auvp_handle* h, int32_t episode, int32_t* sizes /* [K] */
 /* device-side result records for the multi-GPU gather: pointer to [E] auvp_rrt_summary in HBM */
 void* auvp_rrt_summaries_dev(auvp_handle* h);
 
+/* Best-of-K planning: the episodes of the batch that just ran form n_groups groups (one AUV's K trees), group g = episodes
+ * group_off[g] .. group_off[g+1]-1, and the winner of every group is chosen on the device.  The rule is exploring's own
+ * (rrt_dubins.py:101,169: a leaf is kept only if new_cost[0] < opt_cost[0], from inf) folded over the members' best costs in
+ * member order: the lowest best_cost[0], the lowest episode index among equal costs (-0.0 == 0.0); a member without a leaf, or
+ * with a NaN cost, never wins.  The groups partition the batch -- group_off[0] == 0, group_off[n_groups] == E, strictly
+ * increasing -- anything else (an empty group, n_groups < 1) is AUVP_ERR_ARG; without a batch that has run: AUVP_ERR_STATE.
+ * Works after any RRT batch (every mode, every expansion kernel, with or without per-episode limits).
+ * (A struct tag, not a typedef: the record and the entry point share their name.) */
+struct auvp_rrt_group_best {
+  int32_t status;      /* AUVP_OK; AUVP_NO_QUALIFYING_LEAF: no member can win (winner -1); or the status (< 0) of the
+                        * lowest-indexed member that failed on the device */
+  int32_t winner;      /* episode index in the batch, -1: none */
+  int32_t n_with_leaf; /* members with a qualifying leaf */
+  int32_t path_len;    /* the winner's best_path_len, best_cost and best_length (0, inf, 0 without a winner) */
+  double cost[4];
+  double length;
+};
+/* one launch (rrt_group_best_kernel); out [n_groups] may be NULL: the records stay in HBM (auvp_rrt_group_best_dev) */
+int auvp_rrt_group_best(auvp_handle* h, int32_t n_groups, const int32_t* group_off /* [n_groups+1] */,
+                        struct auvp_rrt_group_best* out /* [n_groups], may be NULL */);
+/* the records of the last auvp_rrt_group_best call, [n_groups] in HBM (NULL: none since the batch ran) */
+void* auvp_rrt_group_best_dev(auvp_handle* h);
+/* generate_final_course of the winners only (rrt_group_course_kernel): offsets [n_groups+1] = exclusive prefix sum of the
+ * records' path_len (0 for a group without a winner); out [offsets[n_groups],7] as auvp_rrt_paths.  Offsets that leave a
+ * winner fewer rows than its path_len: AUVP_ERR_ARG.  Before auvp_rrt_group_best (of this batch): AUVP_ERR_STATE. */
+int auvp_rrt_group_paths(auvp_handle* h, const int64_t* offsets, double* out);
+/* the same, left in HBM: out_dev is a device pointer to [offsets[n_groups],7] doubles */
+int auvp_rrt_group_paths_dev(auvp_handle* h, const int64_t* offsets, void* out_dev);
+
 /* ---------------------------------------------------------------------------------------------
  * Planner_RRT (gym_rrt/envs/rrt_dubins.py:34): goal-directed RRT driven by the RL environment.
  * Obstacles come from auvp_world_set (list order matters, :445-451); everything else is here.
