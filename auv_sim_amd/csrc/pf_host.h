@@ -102,13 +102,19 @@ int auvp_pf_set_particles(auvp_handle* h, int32_t F, int32_t N, const double* pa
   if ((rc = pf_alloc(h, P, F, N))) return rc;
   if ((rc = pf_set_rng(h, P, mt, mt_pos))) return rc;
   std::vector<double> soa((size_t)F * 5 * N);
-  std::vector<int32_t> ent((size_t)F * N), ll(F);
+  std::vector<int32_t> ent((size_t)F * N), ll(F), first((size_t)5 * N);
   for (int f = 0; f < F; f++) {
     int mx = N;
+    std::fill(first.begin(), first.end(), -1);  // object id -> the first position that carries it
     for (int p = 0; p < N; p++) {
       for (int c = 0; c < 5; c++) soa[((size_t)f * 5 + c) * N + p] = particles[((size_t)f * N + p) * 5 + c];
       const int id = obj ? obj[(size_t)f * N + p] : p;
       if (id < 0 || id >= 5 * N) return fail(h, AUVP_ERR_ARG, "filter %d position %d: object id %d outside 0..%d", f, p, id, 5 * N - 1);
+      // positions that share an id are ONE Particle object: one state.  Rows that differ (bitwise) have no meaning in the
+      // reference, and the kernel (the first position's row) and the checker (the last one's) would silently disagree
+      if (first[id] < 0) first[id] = p;
+      else if (memcmp(particles + ((size_t)f * N + first[id]) * 5, particles + ((size_t)f * N + p) * 5, 5 * sizeof(double)))
+        return fail(h, AUVP_ERR_ARG, "filter %d: positions %d and %d share object id %d but their rows differ", f, first[id], p, id);
       ent[(size_t)f * N + p] = id;
       if (id + 1 > mx) mx = id + 1;
     }

@@ -183,7 +183,7 @@ __device__ __forceinline__ PfLds pf_carve(unsigned char* smem, int N) {
   L.mt = (uint32_t*)smem;
   L.mt2 = L.mt + 624;
   L.red_i = (int*)(L.mt2 + 624);
-  L.red_d = (double*)(L.red_i + 32);  // red_i [0,16): reductions, 16: choice cursor
+  L.red_d = (double*)(L.red_i + 32);  // red_i [0,16): reductions, 16: choice cursor, 17: empty-list note
   L.etab = L.red_d + 40;              // red_d [0,16): reductions, 16..17: means; etab: auvp_exp_table() (pf_step_kernel)
   L.sx = L.etab + AUVP_EXP_TBL_DOUBLES;
   L.sy = L.sx + n2; L.sv = L.sy + n2; L.sth = L.sv + n2; L.sw = L.sth + n2;
@@ -244,6 +244,7 @@ __global__ __launch_bounds__(T, (T * PPT <= 1280 ? 2 : 1) * T / 256) void pf_ste
   for (int j = 0; j < PPT; j++) if (p0 + j < N) L.off[p0 + j] = D.ent[(size_t)f * N + p0 + j];
   int llen = D.llen[f];
   int status = D.status[f];
+  if (tid == 0) L.red_i[17] = 0;  // set by thread 0 when a step ends on an empty list
   __syncthreads();
 #ifdef AUVP_PF_DIAG  // clocks per section of the step, summed over the launch's steps -> err[k][f] (tools/pf_phases.py --clocks)
   unsigned long long pf_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pf_t0 = __builtin_amdgcn_s_memtime();
@@ -407,7 +408,10 @@ __global__ __launch_bounds__(T, (T * PPT <= 1280 ? 2 : 1) * T / 256) void pf_ste
       for (int j = 0; j < PPT; j++) if (p0 + j < N) { for (int c = 0; c < k[j]; c++) inv[run + c] = p0 + j; run += k[j]; }
       const int len = total;
       __syncthreads();
-      if (len == 0) { status = PF_ERR_EMPTY; break; }  // numpy raises ValueError
+      // numpy raises ValueError: PF_ERR_EMPTY, unless an angle_wrap of this launch failed before -- the first error stays, like
+      // the reference's, whose nan heading ends update_weights before `correct` sees the nan weights.  Noted in LDS and
+      // weighed where the status is written, not in `status`: a second value live out of the step loop made the allocator spill
+      if (len == 0) { if (tid == 0) L.red_i[17] = 1; break; }
       PF_STAMP(3)
       int* cho = L.off;
       if (len == 1) {
@@ -548,7 +552,9 @@ __global__ __launch_bounds__(T, (T * PPT <= 1280 ? 2 : 1) * T / 256) void pf_ste
   }
 #pragma unroll
   for (int j = 0; j < PPT; j++) if (p0 + j < N) D.ent[(size_t)f * N + p0 + j] = L.off[p0 + j];
-  if (__syncthreads_or(status != PF_OK) && tid == 0 && D.status[f] == PF_OK) D.status[f] = status != PF_OK ? status : PF_ERR_ANGLE;
+  // an angle error (any thread's) comes before the empty list that ended the step loop (thread 0's own note)
+  const int angle = __syncthreads_or(status != PF_OK);
+  if (tid == 0 && D.status[f] == PF_OK && (angle || L.red_i[17])) D.status[f] = angle ? PF_ERR_ANGLE : PF_ERR_EMPTY;
   if (tid == 0) { D.mtpos[f] = r.pos; D.llen[f] = llen; D.ndraw[f] += r.drawn; }
 #ifdef AUVP_PF_DIAG
   if (tid == 0) for (int k = 0; k < 7 && k < D.S; k++) D.err[(size_t)k * D.F + f] = (double)pf_acc[k];

@@ -365,7 +365,8 @@ enum { AUVP_PF_UPDATE = 1,  /* ParticleFilter.create_and_update (:277-282) */
 int auvp_pf_create_batch(auvp_handle* h, int32_t n_filters, int32_t n_particles, const double* shark_xy0,
                          const uint32_t* mt_key, const int32_t* mt_pos);
 /* start from caller-supplied lists instead: particles [F,N,5], obj [F,N] or NULL (all distinct),
- * list_len [F] or NULL */
+ * list_len [F] or NULL.  Positions of a filter that share an object id are one Particle object: their
+ * rows must be bitwise identical, else AUVP_ERR_ARG (the message names the filter and both positions). */
 int auvp_pf_set_particles(auvp_handle* h, int32_t n_filters, int32_t n_particles, const double* particles,
                           const int32_t* obj, const int32_t* list_len, const uint32_t* mt_key, const int32_t* mt_pos);
 int auvp_pf_set_rng(auvp_handle* h, const uint32_t* mt_key, const int32_t* mt_pos);
