@@ -288,6 +288,24 @@ def prrt_choose_launch(E, n_cu=256, O=0, freq=10.0, max_step=300, n_buckets=0, f
     return _ask_launch("auvp_prrt_choose_launch", q, _PrrtLaunchChoice(), options, PRRT_KINDS)
 
 
+def forecast_plan(rows, cols, cell_rc):
+    """the level schedule the shark-occupancy forecast walks for prediction1 (auvp_sf_plan; no GPU needed).  cell_rc [C, 2]:
+    (row, column) of every cell of cell_list, in list order.  Returns a dict: level [C] (0 where no 4-neighbour of the cell is
+    earlier in the list, else 1 + the highest level among the earlier neighbours), order [C] (list positions sorted by (level,
+    position)), level_off [n_levels + 1], n_levels.  AuvpError (AUVP_ERR_ARG): a cell outside the grid, a cell listed twice,
+    an empty list."""
+    L = load()
+    L.auvp_sf_plan.argtypes = [C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _ip]
+    rc = np.ascontiguousarray(np.asarray(cell_rc, dtype=np.int32).reshape(-1, 2))
+    n = len(rc)
+    level, order, off = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.int32)
+    nl = C.c_int32()
+    code = L.auvp_sf_plan(int(rows), int(cols), _p(rc, _ip), n, _p(level, _ip), _p(order, _ip), _p(off, _ip), C.byref(nl))
+    if code != 0:
+        raise AuvpError(code, "auvp_sf_plan: a cell outside the %d x %d grid, a cell listed twice, or an empty list" % (rows, cols))
+    return dict(level=level[:n], order=order[:n], level_off=off[:nl.value + 1], n_levels=nl.value)
+
+
 class Context:
     """One planner context = one HIP device + stream + device-resident world and tree storage."""
 

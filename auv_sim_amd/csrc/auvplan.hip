@@ -120,6 +120,8 @@ struct auvp_handle {
   void (*astar_free)(void*) = nullptr;
   void* pf = nullptr;
   void (*pf_free)(void*) = nullptr;
+  void* sf = nullptr;  // shark-occupancy forecast buffers (forecast_host.h)
+  void (*sf_free)(void*) = nullptr;
   void* comm = nullptr;  // RCCL communicator state (gather_host.h)
   void (*comm_free)(void*) = nullptr;
   // Pipeline fallback.  The latency kernels (rrt_trio / rrt_duo, prrt_pipe, the paired astar_kernel) are speculative
@@ -327,6 +329,7 @@ void auvp_destroy(auvp_handle* h) {
   if (h->prrt && h->prrt_free) h->prrt_free(h->prrt);
   if (h->astar && h->astar_free) h->astar_free(h->astar);
   if (h->pf && h->pf_free) h->pf_free(h->pf);
+  if (h->sf && h->sf_free) h->sf_free(h->sf);
   if (h->comm && h->comm_free) h->comm_free(h->comm);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1357,5 +1360,7 @@ PrrtState* prrt_of(auvp_handle* h) {
 #include "sog_kernels.h"
 #include "pf_types.h"
 #include "pf_host.h"
+#include "forecast_kernel.h"
+#include "forecast_host.h"
 #include "compose_host.h"
 #include "gather_host.h"

@@ -389,6 +389,41 @@ int auvp_pf_rng_state(auvp_handle* h, uint32_t* mt_key, int32_t* mt_pos);
  * random.choice drew in correct, :248-250) */
 int auvp_pf_step_log(auvp_handle* h, double* updated, int32_t* choice);
 
+/* ---- shark-occupancy forecast from the particle filters ---------------------------------------------
+ * The link between the filters and the planners' time-binned occupancy table: for every filter, the
+ * chain of SharkUpdate's methods (path_planning/sharkEstimate.py) in ONE launch, one wavefront per
+ * filter, bit for bit what the host methods compute:
+ *   counts      particles per grid entry: list position n counts in [int(qy)][int(qx)], qx = (x - minx) /
+ *               cell_size, qy = (y - miny) / cell_size (cellToIndex's expression), iff 0 <= qx < cols and
+ *               0 <= qy < rows compared in double; nan and out-of-grid particles are not counted
+ *   correction  (:172-199) g = (counts / norm) * prior in the listed cells, total summed in list order,
+ *               every grid entry / total.  total == 0 (ZeroDivisionError): status 1, that filter's
+ *               grids and prob are all zeros, the other filters are unaffected
+ *   rounds      G_0 = the corrected grid, G_{j+1} = prediction1(G_j, stay_prob) (method 1, :56-83) or
+ *               prediction2(G_j, k, P_inf) (method 2, :85-103); P_inf = p_inf [rows,cols], or with NULL
+ *               predictOnAve's grid (1 / n_cells in the listed cells).  Each round is exactly the host
+ *               method; feeding a round's prediction into the next is what SharkUpdate.update's docstring
+ *               intends and its code does not do (its second round raises).
+ * box4 = boundary.bounds; rows / cols as the reference sizes its grids (int(ceil(extent) / cell_size) + 1);
+ * cells [n_cells,4] = bounds of cell_list in list order.  A cell outside the grid (the reference:
+ * IndexError or a wrapped negative index) and a cell listed twice are AUVP_ERR_ARG; rows * cols > 4096 is
+ * AUVP_ERR_CAPACITY.  particles_xy [F,N,2] on the host, or NULL: the particles of this handle's filter
+ * batch, read where they lie in HBM (n_filters / n_particles must be the batch's; AUVP_ERR_STATE without
+ * one).  prior [F,rows,cols], or [rows,cols] with prior_is_shared.  Outputs (each may be NULL): grids
+ * [F,n_rounds+1,rows,cols], prob [F,n_rounds+1,n_cells] = the same values in list order (the layout of
+ * auvp_world_set's prob), counts [F,rows,cols], status [F]. */
+int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t cols, double cell_size, const double* cells,
+                     int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles, const double* prior,
+                     int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k, double norm,
+                     int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status);
+/* The schedule the forecast kernel walks for method 1 (no device needed): cell_rc [n_cells,2] = (row,
+ * column) per list position.  level [n_cells]: 0 where no 4-neighbour is earlier in the list, else 1 + the
+ * highest level among the earlier neighbours; order [n_cells]: list positions sorted by (level, position);
+ * level_off [up to n_cells + 1]: level l = order[level_off[l] .. level_off[l+1]); n_levels.  AUVP_ERR_ARG:
+ * a cell outside the rows x cols grid, a cell listed twice, an empty list. */
+int auvp_sf_plan(int32_t rows, int32_t cols, const int32_t* cell_rc, int32_t n_cells, int32_t* level, int32_t* order,
+                 int32_t* level_off, int32_t* n_levels);
+
 /* standalone evaluations on the device (parity probes for the building blocks) */
 /* RRT.check_collision (:530-549) of n_paths paths; pts [sum(npts),2], path i = pts[off[i]:off[i+1]] */
 int auvp_check_collision_batch(auvp_handle* h, int32_t n_paths, const int32_t* off, const double* pts_xy,
