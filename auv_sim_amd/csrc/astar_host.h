@@ -232,7 +232,8 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (pair && h->pipe_failed()) {
     // the searching wavefront of some instance stopped waiting for its partner (AUVP_ERR_PIPELINE): the batch is searched again
-    // by the one-wavefront kernel, on a fresh epoch of the visited words (same results: tests/test_gpu_astar.py)
+    // by the one-wavefront kernel, on a fresh epoch of the visited words (same results, visited arrays included:
+    // tests/test_gpu_astar_pair.py makes the waits run out under the diagnostic build and counts the instances redone)
     std::vector<auvp::AstarSummary> sm((size_t)E);
     HIPCHK(h, hipMemcpy(sm.data(), B.summary, sm.size() * sizeof(auvp::AstarSummary), hipMemcpyDeviceToHost));
     int n = 0;
@@ -241,7 +242,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
     if (n > 0 && h->opt_flag(OPT_PIPE_FALLBACK, true)) {
       h->pipe_fallback_last = n;
       h->pipe_fallback_total += n;
-      // (255 as above; tests/test_gpu_epoch_wrap.py does not reach this bump: it needs a pipeline that gives up)
+      // (255 as above; tests/test_gpu_astar_pair.py::test_the_redo_clears_the_visited_words_at_the_tag_wrap gives up on batch 255)
       if (S.epoch >= 255u) {
         HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
         S.epoch = 0;

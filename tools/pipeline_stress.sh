@@ -33,7 +33,7 @@ done
 if [ "$ONLY" = "all" ]; then
 # astar_fixLenSOG, paired form: wavefronts 0..3 search, 4..7 are the partners (wave / 4)
 for spec in "2,4,0" "2,4,1"; do
-  run "astar pair (tests/test_gpu_astar.py + dropin)" "$spec,$UNITS,5" "" python -m pytest tests/test_gpu_astar.py tests/test_gpu_dropin_astar.py tests/test_gpu_full_size.py -q -m gpu -k "astar or SOG or sog or fixLen"
+  run "astar pair (soak_astar_pair.py $N cases)" "$spec,$UNITS,5" "" python tests/experiments/soak_astar_pair.py $N 38
 done
 fi
 # waits that run out: the fallback redoes the episodes / instances on the one-wavefront kernels
@@ -44,4 +44,6 @@ fi
 run "prrt_pipe, spin 6" "1,5,1,$UNITS,5" 6 python tests/experiments/soak_planner_duo.py $N 35
 run "prrt_pipe, spin 40" "1,5,4,$UNITS,5" 40 python tests/experiments/soak_planner_duo.py $N 36
 run "prrt_pipe, spin 100" "1,5,3,$UNITS,5" 100 python tests/experiments/soak_planner_duo.py $N 37
-[ "$ONLY" = "all" ] && run "astar pair, spin 6" "2,4,1,$UNITS,5" 6 python -m pytest tests/test_gpu_astar.py tests/test_gpu_dropin_astar.py -q -m gpu
+# (the last line of soak_astar_pair.py counts the instances auvp_astar_batch searched again on the one-wavefront kernel)
+[ "$ONLY" = "all" ] && run "astar pair, spin 6" "2,4,1,$UNITS,5" 6 python tests/experiments/soak_astar_pair.py $N 39
+[ "$ONLY" = "all" ] && run "astar pair, spin 40" "2,4,1,$UNITS,5" 40 python tests/experiments/soak_astar_pair.py $N 40
