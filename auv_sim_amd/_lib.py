@@ -127,6 +127,12 @@ def load():
         L.auvp_rrt_group_best_dev.restype = C.c_void_p
         L.auvp_rrt_group_paths.argtypes = [vp, C.POINTER(C.c_int64), _dp]
         L.auvp_rrt_group_paths_dev.argtypes = [vp, C.POINTER(C.c_int64), C.c_void_p]
+    if hasattr(L, "auvp_world_set_prob_sets"):  # (likewise: probability sets, a table per episode, re-ranking)
+        L.auvp_world_set_prob_sets.argtypes = [vp, C.c_int32, _dp, C.c_void_p]
+        L.auvp_world_prob_set_stats.argtypes = [vp, _dp, _ip]
+        L.auvp_rrt_set_episode_grids.argtypes = [vp, C.c_int32, _ip]
+        L.auvp_rrt_rerank.argtypes = [vp]
+        L.auvp_sf_prob_dev.argtypes = [vp, C.POINTER(C.c_void_p), _ip, _ip, _ip]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -319,6 +325,7 @@ class Context:
         self.n_episodes = 0
         self.max_iter = 0
         self.world_sizes = {}
+        self.n_prob_sets = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -369,20 +376,69 @@ class Context:
         self._chk(self.L.auvp_world_set(self.h, _p(ob), len(ob), _p(hb), len(hb), _p(pg), len(pg), _p(bn), len(bn),
                                         _p(ce), len(ce), _p(pr)))
         self.world_sizes = dict(O=len(ob), H=len(hb), V=len(pg), T=len(bn), C=len(ce))
+        self.n_prob_sets = 0  # (auvp_world_set drops the probability sets)
 
     def set_habitats(self, habitats):
         hb = _f64(habitats if habitats is not None else [], (-1, 3))
         self._chk(self.L.auvp_world_set_habitats(self.h, _p(hb), len(hb)))
         self.world_sizes["H"] = len(hb)
 
+    # ---- probability sets: one shark-occupancy table per tracked shark, all over the world's bins and cells ----
+    def set_prob_sets(self, prob=None, n_sets=None, prob_dev=None):
+        """auvp_world_set_prob_sets: prob [G, T, C] on the host, or prob_dev = a device pointer to n_sets such tables (copied
+        device to device); neither: the sets are cleared.  T and C are the world's."""
+        T, Cn = self.world_sizes.get("T", 0), self.world_sizes.get("C", 0)
+        if prob is None and prob_dev is None:
+            self._chk(self.L.auvp_world_set_prob_sets(self.h, 0, None, None))
+            self.n_prob_sets = 0
+            return
+        if prob is not None:
+            pr = _f64(prob)
+            if pr.ndim != 3 or pr.shape[1:] != (T, Cn):
+                raise ValueError("prob must be [n_sets, %d, %d] (the world's bins and cells), not %r" % (T, Cn, pr.shape))
+            n_sets = pr.shape[0] if n_sets is None else int(n_sets)
+            self._chk(self.L.auvp_world_set_prob_sets(self.h, n_sets, _p(pr), None if prob_dev is None else C.c_void_p(prob_dev)))
+        else:
+            self._chk(self.L.auvp_world_set_prob_sets(self.h, int(n_sets), None, C.c_void_p(prob_dev)))
+        self.n_prob_sets = int(n_sets)
+
+    def prob_set_stats(self, n_sets=None):
+        """(absmax [G], one_sign [G]) of the handle's probability sets, as the device computed them"""
+        n_sets = self.n_prob_sets if n_sets is None else int(n_sets)
+        a, s = np.zeros(max(int(n_sets), 1)), np.zeros(max(int(n_sets), 1), np.int32)
+        self._chk(self.L.auvp_world_prob_set_stats(self.h, _p(a), _p(s, _ip)))
+        return a[:n_sets], s[:n_sets]
+
+    def rrt_set_episode_grids(self, set_of):
+        """episode e of the prepared batch ranks its leaves against set set_of[e]; None clears the assignment"""
+        if set_of is None:
+            self._chk(self.L.auvp_rrt_set_episode_grids(self.h, 0, None))
+            return
+        so = np.ascontiguousarray(np.asarray(set_of, dtype=np.int32).reshape(-1))
+        self._chk(self.L.auvp_rrt_set_episode_grids(self.h, len(so), _p(so, _ip)))
+
+    def rrt_rerank(self, summaries=True):
+        """the leaf ranking alone on the last run's trees, under the current assignment (auvp_rrt_rerank)"""
+        self._chk(self.L.auvp_rrt_rerank(self.h))
+        return self.summaries() if summaries else None
+
+    def sf_prob_dev(self):
+        """(device pointer, F, R + 1, C) of the last forecast's prob on this context (auvp_sf_prob_dev)"""
+        p, f, t, c = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self.L.auvp_sf_prob_dev(self.h, C.byref(p), C.byref(f), C.byref(t), C.byref(c)))
+        return p.value, f.value, t.value, c.value
+
     # ---- RRT.exploring batch ----
     def rrt_explore_batch(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,
                           max_traj_time=500.0, weights=(-3, -3, -4), dist_to_end=2, diff_max=0.5, min_dist=0.5,
                           max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False,
-                          habitat_keep=None, summaries=True):
-        """prepare + run; the summaries, or None with summaries=False (they stay in HBM: rrt_group_best reads them there)"""
+                          habitat_keep=None, summaries=True, shark_set=None):
+        """prepare + run; the summaries, or None with summaries=False (they stay in HBM: rrt_group_best reads them there).
+        shark_set [E]: every episode ranks its leaves against its own probability set (set_prob_sets); the batch then takes
+        the per-episode-limits route, with every habitat kept and one horizon where the caller gave no limits."""
         self.rrt_prepare(init, seeds, n_iter, mode, freq, bin_interval, v, max_traj_time, weights, dist_to_end,
-                         diff_max, min_dist, max_plan_time, points_per_iter, iter_log, leaf_log, phase_clocks, habitat_keep)
+                         diff_max, min_dist, max_plan_time, points_per_iter, iter_log, leaf_log, phase_clocks, habitat_keep,
+                         shark_set)
         self.rrt_run()
         return self.summaries() if summaries else None
 
@@ -393,13 +449,14 @@ class Context:
     def rrt_prepare(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,
                     max_traj_time=500.0, weights=(-3, -3, -4), dist_to_end=2, diff_max=0.5, min_dist=0.5,
                     max_plan_time=None, points_per_iter=0.0, iter_log=False, leaf_log=False, phase_clocks=False,
-                    habitat_keep=None):
+                    habitat_keep=None, shark_set=None):
         """max_traj_time [E] and / or habitat_keep [E] (bit masks over the world's habitat table): every episode plans with its
-        own horizon and habitat list (auvp_rrt_prepare_episodes; the cap is the largest horizon).  Without both: one horizon."""
+        own horizon and habitat list (auvp_rrt_prepare_episodes; the cap is the largest horizon).  Without both: one horizon.
+        shark_set [E]: the episode's probability set (rrt_set_episode_grids, on the per-episode-limits route)."""
         init = _f64(init, (-1, 6))
         E = len(init)
         lim = None
-        if habitat_keep is not None or np.ndim(max_traj_time) > 0:
+        if habitat_keep is not None or np.ndim(max_traj_time) > 0 or shark_set is not None:
             max_traj_time, lim = episode_limits(E, max_traj_time, habitat_keep, self.world_sizes.get("H", 0), mode, iter_log,
                                                 phase_clocks)
         states = None
@@ -428,6 +485,8 @@ class Context:
             self._chk(self.L.auvp_rrt_prepare(self.h, E, _p(init), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
                                               C.byref(p), flags))
         self.n_episodes, self.max_iter = E, int(n_iter)
+        if shark_set is not None:
+            self.rrt_set_episode_grids(shark_set)
 
     def summaries(self):
         out = np.zeros(self.n_episodes, dtype=SUMMARY_DTYPE)

@@ -108,6 +108,15 @@ struct RrtEpisodeLimDev {
   int32_t K, _pad;
 };
 
+// One probability set of a handle (auvp_world_set_prob_sets): a table [T,C] over the world's bins and cells with the two
+// constants of the leaf pass's error bound for THAT table (WorldDev::prob_absmax / prob_one_sign are the world's own table's).
+// Written by prob_set_stats_kernel, read by rrt_leaf_grid_kernel through a kernel argument of its own (as RrtEpisodeLimDev).
+struct RrtProbSetDev {
+  const double* prob;  // [T,C]
+  double absmax;       // nan if any entry is a nan, else max |p|
+  int32_t one_sign, _pad;
+};
+
 struct RrtSummary {  // must match auvp_rrt_summary in include/auvplan.h
   int32_t status, n_nodes, n_points, n_leaves, best_leaf, best_path_len, iters_run, n_candidates;
   double best_cost[4];

@@ -37,6 +37,12 @@ extern "C" hipError_t auvpi_rrt_rows_stream_launch(const auvp::WorldDev* W, cons
                                                    int grid, int block, int lds_max, int lds, int mirror, hipStream_t stream);
 extern "C" hipError_t auvpi_rrt_rows_launch(const auvp::WorldDev* W, const auvp::RrtParamsDev* P, const auvp::RrtBuffers* B, int n_episodes,
                                             int grid, int block, int lds_max, int lds, hipStream_t stream);
+// rrt_leaf_grid_kernel and prob_set_stats_kernel live in leaf_grid_kernels.hip (so that this unit's leaf kernels keep their code)
+extern "C" hipError_t auvpi_rrt_leaf_grid_launch(const auvp::WorldDev* W, const auvp::RrtParamsDev* P, const auvp::RrtBuffers* B, int n_episodes,
+                                                 int mark_words, const auvp::RrtEpisodeLimDev* lim, const int32_t* set_of,
+                                                 const auvp::RrtProbSetDev* sets, int grid, int block, int lds, hipStream_t stream);
+extern "C" hipError_t auvpi_prob_set_stats_launch(const double* prob, long long n_per_set, int n_sets, auvp::RrtProbSetDev* sets,
+                                                  hipStream_t stream);
 
 static_assert(sizeof(auvp_rrt_summary) == sizeof(RrtSummary), "summary layout");
 static_assert(sizeof(struct auvp_rrt_group_best) == sizeof(RrtGroupBest), "group record layout");
@@ -109,6 +115,11 @@ struct auvp_handle {
   bool lim = false;
   DevBuf d_lim;
   std::vector<int32_t> lim_K;
+  // probability sets (auvp_world_set_prob_sets): n_sets tables [T,C] over the world's bins and cells and their records; grids:
+  // the prepared batch has a set per episode (auvp_rrt_set_episode_grids) and its leaf pass is rrt_leaf_grid_kernel
+  int n_sets = 0;
+  bool grids = false;
+  DevBuf d_sets_prob, d_sets_rec, d_set_of;
   double last_ms = 0.0;
   int last_grid = 0, last_block = 0, last_lds = 0;
   // planner families that live in their own headers keep their state behind an opaque pointer
@@ -354,6 +365,8 @@ int auvp_world_set(auvp_handle* h, const double* obstacles, int32_t O, const dou
   if (V == 1 || V == 2) return fail(h, AUVP_ERR_ARG, "boundary polygon with %d vertices (need >= 3, or 0 for none)", V);
   if (T > RRT_MAX_BINS) return fail(h, AUVP_ERR_ARG, "n_bins %d > %d", T, RRT_MAX_BINS);
   HIPCHK(h, hipSetDevice(h->device));
+  h->n_sets = 0;  // the probability sets belonged to the world that goes (its bins and cells)
+  h->grids = false;
   std::vector<double> ox(O), oy(O), ot(O);
   double run = -INFINITY;
   for (int i = O - 1; i >= 0; i--) {  // suffix max of the radii, list order
@@ -721,6 +734,7 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
                             const int32_t* state_index, const auvp_rrt_params* p, int32_t flags, bool lim) {
   if (!h) return AUVP_ERR_ARG;
   h->lim = false;
+  h->grids = false;
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   if (E <= 0 || !init || !p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
   if (p->max_iter <= 0 || !(p->freq >= 0) || p->mode < 0 || p->mode > 2) return fail(h, AUVP_ERR_ARG, "bad params");
@@ -924,7 +938,10 @@ static int rrt_launch_leaf(auvp_handle* h) {
   const int bm_words = h->opt_on(OPT_LEAF_SWEEP_ALL) ? 0 : rrt_leaf_mark_words(B.cap_nodes);
   const int dyn = gl + RRT_LEAF_WAVES * bm_words * 4;
   const int grid = (E + RRT_LEAF_WAVES - 1) / RRT_LEAF_WAVES;
-  if (h->lim) HIPCHK(h, launch_kernel(rrt_leaf_lim_kernel, grid, RRT_LEAF_WAVES * 64, dyn, h->stream, h->W, h->P, B, E, bm_words, h->d_lim.as<RrtEpisodeLimDev>()));
+  if (h->grids)
+    HIPCHK(h, auvpi_rrt_leaf_grid_launch(&h->W, &h->P, &B, E, bm_words, h->d_lim.as<RrtEpisodeLimDev>(), h->d_set_of.as<int32_t>(),
+                                         h->d_sets_rec.as<RrtProbSetDev>(), grid, RRT_LEAF_WAVES * 64, dyn, h->stream));
+  else if (h->lim) HIPCHK(h, launch_kernel(rrt_leaf_lim_kernel, grid, RRT_LEAF_WAVES * 64, dyn, h->stream, h->W, h->P, B, E, bm_words, h->d_lim.as<RrtEpisodeLimDev>()));
   else HIPCHK(h, launch_kernel(rrt_leaf_kernel, grid, RRT_LEAF_WAVES * 64, dyn, h->stream, h->W, h->P, B, E, bm_words));
   return AUVP_OK;
 }
@@ -1066,6 +1083,84 @@ int auvp_rrt_run(auvp_handle* h) {
   rc = n_stream > 0 ? rrt_run_pass(h, false, true) : rrt_run_pass(h, true);
   h->last_ms += first_ms;  // (the time the caller waited)
   return rc;
+}
+
+int auvp_world_set_prob_sets(auvp_handle* h, int32_t n_sets, const double* prob_host, const void* prob_dev) {
+  if (!h) return AUVP_ERR_ARG;
+  if (n_sets == 0 && !prob_host && !prob_dev) {
+    h->n_sets = 0;
+    h->grids = false;
+    return AUVP_OK;
+  }
+  if (n_sets < 1) return fail(h, AUVP_ERR_ARG, "n_sets %d < 1", n_sets);
+  if ((prob_host != nullptr) == (prob_dev != nullptr)) return fail(h, AUVP_ERR_ARG, "exactly one of prob_host and prob_dev must be given");
+  if (!h->have_world || h->W.n_bins < 1 || h->W.n_cells < 1)
+    return fail(h, AUVP_ERR_STATE, "probability sets need a world with time bins and cells (auvp_world_set)");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)h->W.n_bins * (size_t)h->W.n_cells, bytes = (size_t)n_sets * n * sizeof(double);
+  h->n_sets = 0;
+  h->grids = false;  // (an assignment was checked against the sets that go)
+  HIPCHK(h, h->d_sets_prob.reserve(bytes));
+  HIPCHK(h, h->d_sets_rec.reserve((size_t)n_sets * sizeof(RrtProbSetDev)));
+  if (prob_host) HIPCHK(h, hipMemcpyAsync(h->d_sets_prob.p, prob_host, bytes, hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(h, hipMemcpyAsync(h->d_sets_prob.p, prob_dev, bytes, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, auvpi_prob_set_stats_launch(h->d_sets_prob.as<double>(), (long long)n, n_sets, h->d_sets_rec.as<RrtProbSetDev>(), h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->n_sets = n_sets;
+  return AUVP_OK;
+}
+
+int auvp_world_prob_set_stats(auvp_handle* h, double* absmax, int32_t* one_sign) {
+  if (!h) return AUVP_ERR_ARG;
+  if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle");
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<RrtProbSetDev> rec((size_t)h->n_sets);
+  HIPCHK(h, hipMemcpyAsync(rec.data(), h->d_sets_rec.p, rec.size() * sizeof(RrtProbSetDev), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int g = 0; g < h->n_sets; g++) {
+    if (absmax) absmax[g] = rec[(size_t)g].absmax;
+    if (one_sign) one_sign[g] = rec[(size_t)g].one_sign;
+  }
+  return AUVP_OK;
+}
+
+int auvp_rrt_set_episode_grids(auvp_handle* h, int32_t n_episodes, const int32_t* set_of) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!set_of) {
+    h->grids = false;
+    return AUVP_OK;
+  }
+  if (!h->prepared || !h->lim) return fail(h, AUVP_ERR_STATE, "the batch was not prepared by auvp_rrt_prepare_episodes");
+  if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle (auvp_world_set_prob_sets)");
+  if (n_episodes != h->E) return fail(h, AUVP_ERR_ARG, "n_episodes %d, the prepared batch has %d", n_episodes, h->E);
+  for (int e = 0; e < n_episodes; e++)
+    if (set_of[e] < 0 || set_of[e] >= h->n_sets) return fail(h, AUVP_ERR_ARG, "episode %d: set %d outside [0, %d)", e, set_of[e], h->n_sets);
+  HIPCHK(h, hipSetDevice(h->device));
+  h->grids = false;
+  int rc = upload(h, h->d_set_of, set_of, (size_t)n_episodes);
+  if (rc != AUVP_OK) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->grids = true;
+  return AUVP_OK;
+}
+
+int auvp_rrt_rerank(auvp_handle* h) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!h->prepared || !h->have_batch) return fail(h, AUVP_ERR_STATE, "no run has completed since the batch was prepared");
+  HIPCHK(h, hipSetDevice(h->device));
+  h->have_group = false;
+  // the leaf pass alone: it rewrites node_f[6..7], node_c and the summaries' leaf fields from the tree, which it leaves as it is
+  if (h->B.leaf_stats) HIPCHK(h, hipMemsetAsync(h->B.leaf_stats, 0, 8 * sizeof(unsigned long long), h->stream));
+  HIPCHK(h, hipEventRecord(h->ev_mid, h->stream));
+  int rc = rrt_launch_leaf(h);
+  if (rc != AUVP_OK) return rc;
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev_mid, h->ev1));
+  h->last_leaf_ms = ms;
+  h->last_ms = ms;
+  return AUVP_OK;
 }
 
 int auvp_rrt_summaries(auvp_handle* h, auvp_rrt_summary* out) {

@@ -10,6 +10,7 @@ namespace {
 
 struct SfState {
   DevBuf xy, prior, p_inf, cell_g, sched_g, level_off, grids, prob, counts, status;
+  int F = 0, T = 0, C = 0;  // shape of `prob` after the last forecast that completed (F == 0: none)
 };
 
 SfState* sf_of(auvp_handle* h) {
@@ -74,6 +75,7 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   }
   HIPCHK(h, hipSetDevice(h->device));
   SfState& S = *sf_of(h);
+  S.F = 0;  // (auvp_sf_prob_dev: nothing to hand out until this forecast has completed)
   auvp::SfDev D{};
   D.F = F; D.N = N; D.rows = rows; D.cols = cols; D.C = C; D.R = R; D.method = method; D.n_levels = plan.n_levels;
   D.prior_shared = prior_is_shared ? 1 : 0;
@@ -116,6 +118,18 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms; h->last_grid = F; h->last_block = 64; h->last_lds = (int)lds;
+  S.F = F; S.T = (int)T; S.C = C;
+  return AUVP_OK;
+}
+
+int auvp_sf_prob_dev(auvp_handle* h, const void** prob_dev, int32_t* n_filters, int32_t* n_bins, int32_t* n_cells) {
+  if (!h) return AUVP_ERR_ARG;
+  const SfState* S = static_cast<const SfState*>(h->sf);
+  if (!S || S->F < 1) return fail(h, AUVP_ERR_STATE, "no forecast has run on this handle");
+  if (prob_dev) *prob_dev = S->prob.p;
+  if (n_filters) *n_filters = S->F;
+  if (n_bins) *n_bins = S->T;
+  if (n_cells) *n_cells = S->C;
   return AUVP_OK;
 }
 

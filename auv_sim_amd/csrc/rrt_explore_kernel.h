@@ -577,6 +577,9 @@ __host__ __device__ inline int rrt_leaf_mark_words(int cap_nodes) {
   return w <= 4096 ? w : 0;
 }
 
+// (leaf_grid_kernels.hip includes this header for the body's helpers and defines its own instance of the body: it leaves these two
+// out, AUVP_LEAF_KERNELS_ELSEWHERE, so that the library holds one copy of each)
+#ifndef AUVP_LEAF_KERNELS_ELSEWHERE
 static __global__ __launch_bounds__(RRT_LEAF_WAVES * 64) __attribute__((amdgpu_waves_per_eu(AUVP_LEAF_WPE, AUVP_LEAF_WPE))) void rrt_leaf_kernel(WorldDev W, RrtParamsDev P, RrtBuffers B, int n_episodes,
                                                                       int mark_words) {
   constexpr bool LIM = false;
@@ -592,6 +595,7 @@ static __global__ __launch_bounds__(RRT_LEAF_WAVES * 64) __attribute__((amdgpu_w
   constexpr bool LIM = true;
 #include "rrt_leaf_body.h"
 }
+#endif  // AUVP_LEAF_KERNELS_ELSEWHERE
 
 // generate_final_course (:321-331) of episode ep's best leaf, written root -> leaf (exploring reverses it, :174) from o on: one
 // wavefront walks leaf -> root and fills the elements from the back (nothing is written for an episode without a leaf)

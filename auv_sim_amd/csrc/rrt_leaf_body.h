@@ -1,7 +1,8 @@
-// rrt_leaf_body.h -- the body of rrt_leaf_kernel and rrt_leaf_lim_kernel (rrt_explore_kernel.h), included inside both.
+// rrt_leaf_body.h -- the body of rrt_leaf_kernel and rrt_leaf_lim_kernel (rrt_explore_kernel.h), included inside both, and of
+// rrt_leaf_grid_kernel (leaf_grid_kernels.hip), which defines AUVP_LEAF_GRID around its include and brings set_of and sets.
 // In scope: the kernel arguments W, P, B, n_episodes, mark_words, lim and the compile-time constant LIM.
-// (One text in two kernels, not a __device__ function: the function form changed rrt_leaf_kernel's register allocation.)
-// No include guard: the file is included once inside each of the two kernels, and nowhere else.
+// (One text in three kernels, not a __device__ function: the function form changed rrt_leaf_kernel's register allocation.)
+// No include guard: the file is included once inside each of the kernels, and nowhere else.
   __shared__ __align__(16) unsigned char tables[RRT_WORLD_BYTES + RRT_MAX_HAB * 32 + RRT_MAX_POLY * 16 + RRT_MAX_BINS * 16];
   __shared__ double w_term[RRT_LEAF_WAVES][64];
   __shared__ double w_S[RRT_LEAF_WAVES][64];
@@ -24,6 +25,19 @@
   __syncthreads();
   const int ep = (int)blockIdx.x * RRT_LEAF_WAVES + wave;
   if (ep >= n_episodes) return;  // no workgroup barrier after this point
+#ifdef AUVP_LEAF_GRID
+  {
+    // rrt_leaf_grid_kernel only (the other two kernels never see these lines): the episode's own probability table and the two
+    // constants of the error bound that belong to it, swapped into the by-value copy of the world.  The record is fetched at a
+    // wave-uniform address and every word goes through readfirstlane: the table's base stays in scalar registers.
+    const RrtProbSetDev* rec = sets + uni(set_of[ep]);
+    const unsigned long long pb = reinterpret_cast<unsigned long long>(rec->prob);
+    W.prob = reinterpret_cast<const double*>(((unsigned long long)(uint32_t)uni((int)(uint32_t)(pb >> 32)) << 32) |
+                                             (unsigned long long)(uint32_t)uni((int)(uint32_t)(pb & 0xffffffffull)));
+    W.prob_absmax = readfirst_f64(rec->absmax);
+    W.prob_one_sign = uni(rec->one_sign);
+  }
+#endif
   uint32_t* mark = mark_words > 0 ? reinterpret_cast<uint32_t*>(leaf_dyn + rrt_leaf_grid_lds_bytes(W.sg_enabled, W.sg_ncol, W.sg_nrow)) +
                                         (size_t)wave * mark_words
                                   : nullptr;

@@ -71,6 +71,27 @@ def habitat_keep_bits(masks, n_habitats, n_episodes):
     return [int(m) for m in masks]
 
 
+def shark_set_indices(shark_of, n, n_sets, timebin=True):
+    """shark_of -> [n] int32 indices into the planner's shark tables (RRT.set_shark_grids), checked without a device: ValueError
+    for another mode than time-bin (the tables ride on the per-episode-limits route), without tables, for a wrong length, a
+    value that is no integer, or an index outside [0, n_sets)."""
+    if not timebin:
+        raise ValueError("shark_of needs time-bin mode (plan_time=True, traj_time_stamp=True)")
+    if n_sets < 1:
+        raise ValueError("shark_of given, but the planner has no shark tables (set_shark_grids)")
+    idx = list(shark_of)
+    if len(idx) != n:
+        raise ValueError("shark_of has %d entries, expected %d" % (len(idx), n))
+    out = np.zeros(n, dtype=np.int32)
+    for i, g in enumerate(idx):
+        if isinstance(g, bool) or int(g) != g:
+            raise ValueError("shark_of[%d] = %r is not an integer" % (i, g))
+        if not 0 <= int(g) < n_sets:
+            raise ValueError("shark_of[%d] = %d outside [0, %d)" % (i, int(g), n_sets))
+        out[i] = int(g)
+    return out
+
+
 def first_bucket_commit(course_t, course_xy, t0, max_traj_time, round_span, keep, habitats_xys):
     """One round of replanning's host step (rrt_dubins.py:82-87) on arrays: the points of the course that splitPath
     (:590-602) puts into its first bucket, and removeHabitat (:604-610) applied to the episode's habitat list given as the
@@ -138,6 +159,53 @@ class RRT:
         self._cost_ctx = None   # cost-only context of replanning() (created on first use)
         self._last = None       # (summary, initial, E index) of the last exploring call
         self._mps_cache = None
+        self._set_prob = None   # host copy [G, T, C] of the shark tables of set_shark_grids (None: none)
+        self._batch = None      # what rerank needs of the last exploring_batch: (initials, shark_interval, max_traj_time)
+
+    @property
+    def n_shark_sets(self):
+        return 0 if self._set_prob is None else len(self._set_prob)
+
+    def set_shark_grids(self, grids):
+        """One shark-occupancy table per tracked shark, for shark_of: a list of sharkGrid dicts with the constructor's bin
+        keys and cell order, or a sharkForecast.Forecast -- then its prob [F, R+1, C] goes from the forecast's context to
+        the planner's without leaving HBM (R + 1 must be the planner's bin count and the cell list the planner's).  ValueError
+        otherwise.  None or an empty list clears the tables.  The constructor's own grid stays the table of every call
+        without shark_of."""
+        if grids is None or (isinstance(grids, (list, tuple)) and len(grids) == 0):
+            self._ctx.set_prob_sets()
+            self._set_prob = None
+            return
+        T, Cn = len(self._bins), len(self._cells)
+        if hasattr(grids, "prob") and hasattr(grids, "cell_bounds"):  # a Forecast
+            fc = grids
+            if fc.prob.ndim != 3 or fc.prob.shape[1] != T:
+                raise ValueError("the forecast has %d time bins (rounds + 1), the planner %d" % (fc.prob.shape[1], T))
+            cb = np.array(fc.cell_bounds, dtype=np.float64).reshape(-1, 4)
+            if cb.shape != self._cells.shape or not np.array_equal(cb, self._cells):
+                raise ValueError("the forecast's cell list is not the planner's")
+            src = getattr(fc, "ctx", None)
+            if src is not None and src.device == self._ctx.device and getattr(src, "sf_serial", None) == getattr(fc, "serial", -1):
+                ptr, F, Tf, Cf = src.sf_prob_dev()
+                if (F, Tf, Cf) != fc.prob.shape:
+                    raise ValueError("the forecast's device copy is [%d, %d, %d], not %r" % (F, Tf, Cf, fc.prob.shape))
+                self._ctx.set_prob_sets(n_sets=F, prob_dev=ptr)
+            else:  # (a forecast of another device, or one its context has since replaced: from the host copy)
+                self._ctx.set_prob_sets(fc.prob)
+            self._set_prob = np.array(fc.prob, dtype=np.float64)
+            return
+        tabs = []
+        for g, grid in enumerate(grids):
+            bins, cells, prob = pack_shark_grid(grid)
+            if bins.shape != self._bins.shape or not np.array_equal(bins, self._bins):
+                raise ValueError("shark grid %d: its time bins are not the constructor's" % g)
+            if cells.shape != self._cells.shape or not np.array_equal(cells, self._cells):
+                raise ValueError("shark grid %d: its cells are not the constructor's, in the constructor's order" % g)
+            tabs.append(prob)
+        if T == 0 or Cn == 0:
+            raise ValueError("shark tables need a planner whose own grid has time bins and cells")
+        self._set_prob = np.stack(tabs)
+        self._ctx.set_prob_sets(self._set_prob)
 
     # ------------------------------------------------------------------ reference API
     def exploring(self, initial, habitats, plot_interval, bin_interval, v, shark_interval, traj_time_stamp=False,
@@ -154,14 +222,18 @@ class RRT:
 
     def exploring_batch(self, initials, habitats, plot_interval, bin_interval, v, shark_interval,
                         traj_time_stamp=False, max_plan_time=5, max_traj_time=200.0, plan_time=True,
-                        weights=[-1, -1, -1], max_iter=None, seeds=None, habitat_masks=None):
+                        weights=[-1, -1, -1], max_iter=None, seeds=None, habitat_masks=None, shark_of=None):
         """E independent exploring() calls in one launch (one wavefront per episode).  Returns a list of
         result dicts (None where the reference would have raised for lack of a qualifying leaf).
+
+        shark_of [E] (time-bin mode): episode e ranks its leaves against table shark_of[e] of set_shark_grids and equals
+        exploring() of an RRT built with that table.  The tree does not depend on the table.
 
         Per-episode limits (time-bin mode): max_traj_time [E] gives every episode its own horizon, habitat_masks ([E] ints,
         bit h = habitats[h], or [E, H] booleans) its own habitat list -- the subsequence of `habitats` its mask selects.
         Episode e then equals exploring(initials[e], [its habitats], ..., max_traj_time=max_traj_time[e])."""
         E = len(initials)
+        sets = None if shark_of is None else shark_set_indices(shark_of, E, self.n_shark_sets, bool(plan_time and traj_time_stamp))
         if max_iter is None:
             max_iter = max(1, int(math.ceil(max_plan_time * self.iters_per_second)))
         use_global = seeds is None
@@ -173,11 +245,29 @@ class RRT:
         else:
             seed_arg = np.array([int(s) for s in seeds], dtype=np.uint64)
         summ = self._explore_summaries(initials, habitats, bin_interval, v, traj_time_stamp, max_traj_time, plan_time, weights,
-                                       max_iter, seed_arg, habitat_masks)
+                                       max_iter, seed_arg, habitat_masks, shark_set=sets)
         if use_global:
             n = int(summ[0]["n_draw32"])
             if n:
                 random.getrandbits(32 * n)  # advance the global stream by what the device consumed
+        self._batch = (list(initials), shark_interval, max_traj_time)
+        return self._batch_results(summ)
+
+    def rerank(self, shark_of):
+        """The last exploring_batch's trees ranked again, every episode against table shark_of[e] (None: the constructor's
+        grid): what exploring_batch would return with that shark_of, for the price of the leaf pass -- no tree is grown.  The
+        batch must have gone the per-episode-limits route (shark_of, habitat_masks or max_traj_time [E]) for a table per
+        episode; AuvpError (AUVP_ERR_STATE) otherwise, or without a batch."""
+        if self._batch is None:
+            raise _lib.AuvpError(-4, "no exploring_batch to rank again")
+        sets = None if shark_of is None else shark_set_indices(shark_of, len(self._batch[0]), self.n_shark_sets)
+        self._ctx.rrt_set_episode_grids(sets)
+        return self._batch_results(self._ctx.rrt_rerank())
+
+    def _batch_results(self, summ):
+        """the result dicts of exploring_batch from the summaries of the batch self._batch describes"""
+        initials, shark_interval, max_traj_time = self._batch
+        E = len(initials)
         bad = summ["status"] < 0
         if bad.any():
             e = int(np.argmax(bad))
@@ -202,7 +292,7 @@ class RRT:
         return out
 
     def _explore_summaries(self, initials, habitats, bin_interval, v, traj_time_stamp, max_traj_time, plan_time, weights,
-                           max_iter, seed_arg, habitat_masks=None, summaries=True):
+                           max_iter, seed_arg, habitat_masks=None, summaries=True, shark_set=None):
         """one prepare + run of exploring episodes on this object's context; the summaries (statuses unchecked), or None with
         summaries=False: they stay in HBM (best-of-K planning reads them there)"""
         mode = "timebin" if (plan_time and traj_time_stamp) else ("plantime" if plan_time else "nn")
@@ -211,23 +301,25 @@ class RRT:
         init = np.array([[float(m.x), float(m.y), float(m.theta), float(m.traj_time_stamp),
                           float(m.plan_time_stamp), float(m.length)] for m in initials], dtype=np.float64).reshape(-1, 6)
         keep = None
+        self._batch = None  # (rerank follows an exploring_batch only)
         if habitat_masks is not None or np.ndim(max_traj_time) > 0:  # per-episode limits
             keep = np.array(habitat_keep_bits(habitat_masks, len(hab), len(init)), dtype=np.uint64)
         return self._ctx.rrt_explore_batch(init, seed_arg, int(max_iter), mode=mode, freq=self.freq,
                                            bin_interval=bin_interval, v=v, max_traj_time=max_traj_time,
                                            weights=weights, dist_to_end=self.dist_to_end, diff_max=self.diff_max,
                                            min_dist=0.5, max_plan_time=float(max_iter),  # virtual clock: 1 tick per iteration
-                                           habitat_keep=keep, **({} if summaries else {"summaries": False}))
+                                           habitat_keep=keep, shark_set=shark_set, **({} if summaries else {"summaries": False}))
 
     def exploring_best_of(self, initials, habitats, plot_interval, bin_interval, v, shark_interval, traj_time_stamp=False,
                           max_plan_time=5, max_traj_time=200.0, plan_time=True, weights=[-1, -1, -1], max_iter=None,
-                          seeds=None, habitat_masks=None):
+                          seeds=None, habitat_masks=None, shark_of=None):
         """Best of K trees for each of N AUVs in one launch: seeds [N][K]; AUV i's members are the batch's episodes i*K ..
         i*K+K-1, each an ordinary exploring episode from initials[i] with seeds[i][m] (and max_traj_time[i], habitat_masks[i]
         where those are per AUV, as in exploring_batch).  The winner is exploring's own rule folded over the members in order
         (the lowest cost, the earliest member among equal costs), chosen on the device; only the winners' courses are copied to
         the host and turned into objects.  Returns N dicts shaped like exploring's plus "tree", the winning member's index;
-        None where no member has a qualifying leaf.  A member that failed on the device raises AuvpError."""
+        None where no member has a qualifying leaf.  A member that failed on the device raises AuvpError.
+        shark_of [N]: AUV i's K trees are all ranked against table shark_of[i] of set_shark_grids."""
         N = len(initials)
         if seeds is None or len(seeds) != N or N == 0:
             raise ValueError("seeds [N][K] are required: one row of K seeds per AUV")
@@ -236,6 +328,8 @@ class RRT:
             raise ValueError("every AUV needs the same number (>= 1) of seeds")
         if max_iter is None:
             max_iter = max(1, int(math.ceil(max_plan_time * self.iters_per_second)))
+        sets = None if shark_of is None else np.repeat(shark_set_indices(shark_of, N, self.n_shark_sets,
+                                                                         bool(plan_time and traj_time_stamp)), K)
         seed_arg = np.array([int(s) for row in seeds for s in row], dtype=np.uint64)
         members = [initials[i] for i in range(N) for _ in range(K)]
         per_auv = habitat_masks is not None or np.ndim(max_traj_time) > 0
@@ -243,7 +337,7 @@ class RRT:
         mtt = np.repeat(horizons, K) if per_auv else max_traj_time
         masks = np.repeat(np.array(habitat_keep_bits(habitat_masks, len(habitats), N), dtype=object), K).tolist() if per_auv else None
         self._explore_summaries(members, habitats, bin_interval, v, traj_time_stamp, mtt, plan_time, weights, max_iter,
-                                seed_arg, masks, summaries=False)
+                                seed_arg, masks, summaries=False, shark_set=sets)
         best = self._ctx.rrt_group_best(np.arange(N + 1, dtype=np.int64) * K)
         bad = best["status"] < 0
         if bad.any():
@@ -307,7 +401,7 @@ class RRT:
         return [committed[1:], rounds, total]
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
-                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1):
+                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None):
         """N independent replanning() loops, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
@@ -325,8 +419,12 @@ class RRT:
         plan from its committed state with its horizon and habitat list -- and commits the first bucket of the best one (the
         rule of exploring_best_of, chosen on the device; only the winners' courses reach the host).  round_tree names the
         winning member of each round.  An AUV without a winner in some round gets None.  Seeds only: one generator cannot
-        continue K streams, so rngs raises ValueError."""
+        continue K streams, so rngs raises ValueError.
+
+        shark_of [N]: AUV e plans every round against table shark_of[e] of set_shark_grids, and its whole trajectory's cost
+        is taken against that table (one cost launch per table in use); entry e equals the call on an RRT built with it."""
         N = len(starts)
+        sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
         K = int(trees_per_auv)
         if K < 1:
             raise ValueError("trees_per_auv must be >= 1")
@@ -366,10 +464,10 @@ class RRT:
             mtt = np.array([ttl[e] + last[e][4] for e in act], dtype=np.float64)
             if K > 1:
                 status, best_cost, tree, paths = self._replan_round_best_of(act, K, streams, last, all_habitats, mtt, keep, weight,
-                                                                            max_iter)
+                                                                            max_iter, None if sets is None else sets[act])
             else:
                 status, best_cost, tree, paths = self._replan_round(act, streams, gens, last, all_habitats, mtt, keep, weight,
-                                                                    max_iter)
+                                                                    max_iter, None if sets is None else sets[act])
             for i, e in enumerate(act):
                 if status[i] == _lib.NO_QUALIFYING_LEAF:
                     alive[e] = False
@@ -401,11 +499,14 @@ class RRT:
             rows = {e: (np.concatenate(traj[e]) if as_arrays and traj[e] else
                         np.array([[m.x, m.y, m.theta, m.v, m.traj_time_stamp, m.plan_time_stamp, m.length] for m in traj[e]],
                                  dtype=np.float64).reshape(-1, 7)) for e in done}
-            self._cost_ctx.set_world(None, hab, None, self._bins, self._cells, self._prob)
-            out = self._cost_ctx.cost_paths([rows[e][:, [0, 1, 4]] for e in done], [0] * len(done), [len(self._bins)] * len(done),
-                                            [float(rows[e][-1, 4]) if len(rows[e]) else float(last[e][4]) for e in done],
-                                            [[-3.0, -3.0, -4.0]] * len(done))
-            costs = {e: out[i] for i, e in enumerate(done)}
+            # (with shark_of: the AUVs grouped by table, one launch per table in use, each against its own table)
+            for g in ([None] if sets is None else sorted(set(int(sets[e]) for e in done))):
+                grp = done if g is None else [e for e in done if int(sets[e]) == g]
+                self._cost_ctx.set_world(None, hab, None, self._bins, self._cells, self._prob if g is None else self._set_prob[g])
+                out = self._cost_ctx.cost_paths([rows[e][:, [0, 1, 4]] for e in grp], [0] * len(grp), [len(self._bins)] * len(grp),
+                                                [float(rows[e][-1, 4]) if len(rows[e]) else float(last[e][4]) for e in grp],
+                                                [[-3.0, -3.0, -4.0]] * len(grp))
+                costs.update({e: out[i] for i, e in enumerate(grp)})
         res = []
         for e in range(N):
             if traj[e] is None:
@@ -424,7 +525,7 @@ class RRT:
                             [all_habitats[h] for h in range(H) if (keep[e] >> h) & 1]])
         return res
 
-    def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter):
+    def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
         """one round of replanning_batch, one tree per active AUV: (status [A], best_cost [A,4], tree [A] = 0, courses)"""
         round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
         if all(gens[e] is None for e in act):
@@ -435,7 +536,7 @@ class RRT:
             seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
         init_objs = [_Init(last[e]) for e in act]
         summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, mtt, True, weight, max_iter, seed_arg,
-                                       [keep[e] for e in act])
+                                       [keep[e] for e in act], shark_set=sets)
         for i, e in enumerate(act):
             n = int(summ[i]["n_draw32"])
             if gens[e] is not None and n:
@@ -447,13 +548,14 @@ class RRT:
         paths = self._ctx.paths(summ)
         return summ["status"], summ["best_cost"], np.zeros(len(act), dtype=np.int64), paths
 
-    def _replan_round_best_of(self, act, K, streams, last, all_habitats, mtt, keep, weight, max_iter):
+    def _replan_round_best_of(self, act, K, streams, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
         """one round with K trees per active AUV: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s members; the winners are
         chosen on the device and only their courses are copied.  Returns as _replan_round, tree = the winning member."""
         seed_arg = np.array([streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
         init_objs = [_Init(last[e]) for e in act for _ in range(K)]
         self._explore_summaries(init_objs, all_habitats, 5, 2, True, np.repeat(mtt, K), True, weight, max_iter, seed_arg,
-                                [keep[e] for e in act for _ in range(K)], summaries=False)
+                                [keep[e] for e in act for _ in range(K)], summaries=False,
+                                shark_set=None if sets is None else np.repeat(sets, K))
         best = self._ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
         bad = best["status"] < 0
         if bad.any():

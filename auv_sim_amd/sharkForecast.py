@@ -17,9 +17,13 @@ docstring intends ("one prediction per time bin of the trajectory") and what its
 Limits, documented: rows x cols <= 4096 (`AUVP_ERR_CAPACITY` above); a cell may be listed once (the reference would visit
 it twice and see neighbours that come later in the list; `AUVP_ERR_ARG` here); a cell outside the grid is `AUVP_ERR_ARG`
 (the reference: IndexError, or a silently wrapped negative index).  The particles are read where `FilterBatch` keeps them in
-HBM (or from an [F, N, 2] host array); the forecast comes back to the host, and goes to the planners through the existing
-`set_world` / `RRT(...)` path as the dict `shark_grid` builds -- a world keeps ONE grid.  No CPU path: raises without the
-library / a GPU.
+HBM (or from an [F, N, 2] host array); the forecast comes back to the host, and goes to a planner in one of two ways: one
+filter's table as the dict `shark_grid` builds, through `RRT(...)`, or ALL F tables at once through
+`RRT.set_shark_grids(forecast)` -- the device copy of `prob` is handed from this context to the planner's without leaving
+HBM (`auvp_sf_prob_dev` -> `auvp_world_set_prob_sets`), and `shark_of=[...]` on `exploring_batch` / `exploring_best_of` /
+`replanning_batch` then plans every AUV of a batch against its own shark's forecast in the same launch.  A world still keeps
+ONE grid of its own (the constructor's); the F tables are probability sets beside it, over the same bins and cells.  No CPU
+path: raises without the library / a GPU.
 """
 import ctypes as C
 import math
@@ -36,9 +40,11 @@ class Forecast:
     """what `SharkForecast.run` returns: grids [F, R+1, rows, cols], prob [F, R+1, C] (the same values in cell_list order: the
     planners' layout), counts [F, rows, cols] int32, status [F] (0, or ZERO_TOTAL: that filter's grids are all zeros)"""
 
-    def __init__(self, grids, prob, counts, status, cell_bounds, kernel_ms):
+    def __init__(self, grids, prob, counts, status, cell_bounds, kernel_ms, ctx=None, serial=None):
         self.grids, self.prob, self.counts, self.status = grids, prob, counts, status
         self.cell_bounds, self.kernel_ms = cell_bounds, kernel_ms
+        # the context that holds prob's device copy while `serial` is still its latest forecast (RRT.set_shark_grids)
+        self.ctx, self.serial = ctx, serial
 
     def shark_grid(self, f, curr, bin_interval):
         """filter f's forecast as the planners' dict {(t0 + j*bin, t1 + j*bin): {cell.bounds: prob}}, j = 0 .. rounds, curr =
@@ -125,7 +131,8 @@ class SharkForecast:
                                     _lib._p(p_inf) if p_inf is not None else None, float(stay_prob), float(k), float(norm), R,
                                     _lib._p(grids), _lib._p(prob), _lib._p(counts, _ip), _lib._p(status, _ip)))
         self.last = Forecast(grids.reshape(F, R + 1, rows, cols), prob.reshape(F, R + 1, n_cells), counts.reshape(F, rows, cols),
-                             status, self.cell_bounds, ctx.last_kernel_ms())
+                             status, self.cell_bounds, ctx.last_kernel_ms(), ctx, getattr(ctx, "sf_serial", 0) + 1)
+        ctx.sf_serial = self.last.serial
         return self.last
 
     def shark_grid(self, f, curr, bin_interval):

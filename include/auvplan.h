@@ -180,6 +180,30 @@ int auvp_rrt_group_paths(auvp_handle* h, const int64_t* offsets, double* out);
 /* the same, left in HBM: out_dev is a device pointer to [offsets[n_groups],7] doubles */
 int auvp_rrt_group_paths_dev(auvp_handle* h, const int64_t* offsets, void* out_dev);
 
+/* Probability sets: a fleet that tracks several sharks plans every AUV against its own shark's occupancy table.
+ * auvp_world_set_prob_sets puts n_sets tables [n_sets, T, C] on the handle; they share the world's bins [T] and cells [C]
+ * (AUVP_ERR_STATE without a world that has both).  Exactly one of prob_host and prob_dev is non-NULL (both or neither:
+ * AUVP_ERR_ARG); prob_dev is a device pointer on the handle's device and is copied device to device into a buffer the handle
+ * owns, so the caller's buffer is free again when the call returns.  n_sets < 1 is AUVP_ERR_ARG, except n_sets == 0 with both
+ * pointers NULL, which clears the sets.  Per set, a small kernel computes what auvp_world_set computes for its one table: absmax
+ * (nan if any entry is a nan, else max |p|) and one_sign (1 unless there is a nan or both signs occur) -- the constants of the
+ * leaf pass's error bound, each episode's own.  A later auvp_world_set drops the sets; auvp_world_set_habitats keeps them.
+ * The tree growth never reads a probability table: only the leaf ranking depends on the set. */
+int auvp_world_set_prob_sets(auvp_handle* h, int32_t n_sets, const double* prob_host, const void* prob_dev);
+/* the per-set constants, absmax [n_sets] and one_sign [n_sets] (each may be NULL); AUVP_ERR_STATE without sets */
+int auvp_world_prob_set_stats(auvp_handle* h, double* absmax, int32_t* one_sign);
+/* After auvp_rrt_prepare_episodes and before auvp_rrt_run: episode e ranks its leaves against set set_of[e].  An index outside
+ * [0, n_sets) or n_episodes other than the prepared batch's: AUVP_ERR_ARG; no sets on the handle, or a batch not prepared by
+ * auvp_rrt_prepare_episodes: AUVP_ERR_STATE.  set_of == NULL clears the assignment (the world's own table again); so does every
+ * new prepare and every auvp_world_set_prob_sets.  A call that fails launches nothing. */
+int auvp_rrt_set_episode_grids(auvp_handle* h, int32_t n_episodes, const int32_t* set_of /* [n_episodes] or NULL */);
+/* The leaf ranking alone on the finished trees of the last auvp_rrt_run, with the current assignment (the world's table if
+ * there is none): a tree grown once is ranked against another shark's forecast for the price of the leaf pass.  Rewrites the
+ * summaries' leaf fields (n_leaves, best_leaf, best_path_len, best_cost, best_length, leaf_elems); summaries, paths,
+ * group_best and group_paths work after it (group_best has to be called again).  AUVP_ERR_STATE if no run has completed since
+ * the batch was prepared. */
+int auvp_rrt_rerank(auvp_handle* h);
+
 /* ---------------------------------------------------------------------------------------------
  * Planner_RRT (gym_rrt/envs/rrt_dubins.py:34): goal-directed RRT driven by the RL environment.
  * Obstacles come from auvp_world_set (list order matters, :445-451); everything else is here.
@@ -416,6 +440,12 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
                      int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles, const double* prior,
                      int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k, double norm,
                      int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status);
+/* The device copy of the last forecast's prob [n_filters, n_rounds+1, n_cells], for auvp_world_set_prob_sets(prob_dev) of a
+ * planner's handle: the tables go from the forecast to the planner without leaving HBM.  auvp_sf_forecast synchronises its
+ * stream before it returns, so a copy enqueued afterwards on another handle's stream on the same device is ordered behind the
+ * forecast.  The pointer is valid until the next auvp_sf_forecast on this handle or its destruction.  AUVP_ERR_STATE without a
+ * completed forecast.  Each output may be NULL. */
+int auvp_sf_prob_dev(auvp_handle* h, const void** prob_dev, int32_t* n_filters, int32_t* n_bins, int32_t* n_cells);
 /* The schedule the forecast kernel walks for method 1 (no device needed): cell_rc [n_cells,2] = (row,
  * column) per list position.  level [n_cells]: 0 where no 4-neighbour is earlier in the list, else 1 + the
  * highest level among the earlier neighbours; order [n_cells]: list positions sorted by (level, position);
