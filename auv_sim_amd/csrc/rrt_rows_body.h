@@ -475,7 +475,11 @@
     else cull_and_test(std::false_type{});
     // boundary: strictly inside an axis-aligned rectangle implies Point.within; otherwise the crossing test per point
     const double* sb = S.world->safe_box;
-    const bool box_inside = W.has_safe_box && ex0 > sb[0] && ey0 > sb[1] && ex1 < sb[2] && ey1 < sb[3];
+    // (the four bounds are read together and the compares joined without short circuits: as `a && b && ...` every bound was
+    // an LDS read of its own behind the compare before it -- four round trips in a row, each with its lgkmcnt(0), in every trip:
+    // profiles/rows_trip_lgkm.md.  Without a box the four values are whatever the table holds and the flag decides)
+    const double sb0 = sb[0], sb1 = sb[1], sb2 = sb[2], sb3 = sb[3];
+    const bool box_inside = (W.has_safe_box != 0) & (ex0 > sb0) & (ey0 > sb1) & (ex1 < sb2) & (ey1 < sb3);
     bool outside = false;
     if (wave_any(live && !box_inside)) {
       // lane = path point (two passes' points + the parent's end on lane 15); edges of the polygon one at a time
