@@ -1,5 +1,5 @@
 // astar_host.h -- C-ABI entry points for the A* variants (auvp_astar_*), host side.
-// Included at the end of auvplan.hip (same translation unit: uses auvp_handle, fail, HIPCHK, upload).
+// Included at the end of auvplan.hip (same translation unit: uses auvp_handle, fail, HIPCHK, upload; sq_threshold is world_tables.h's).
 #ifndef AUVP_ASTAR_HOST_H
 #define AUVP_ASTAR_HOST_H
 
@@ -45,11 +45,11 @@ int astar_build_world(auvp_handle* h, AstarState& S) {
   std::vector<double> ox(O), oy(O), ot(O), hab((size_t)H * 4), rc((size_t)C * 4), topn((size_t)T * (C + 1));
   for (int i = 0; i < O; i++) {
     ox[i] = h->w_obst[3 * i]; oy[i] = h->w_obst[3 * i + 1];
-    ot[i] = sq_threshold(h->w_obst[3 * i + 2]);  // plain `d <= obstacle.size` per obstacle (no shared dList here)
+    ot[i] = auvp::sq_threshold(h->w_obst[3 * i + 2]);  // plain `d <= obstacle.size` per obstacle (no shared dList here)
   }
   for (int i = 0; i < H; i++) {
     hab[4 * i] = h->w_hab[3 * i]; hab[4 * i + 1] = h->w_hab[3 * i + 1]; hab[4 * i + 2] = h->w_hab[3 * i + 2];
-    hab[4 * i + 3] = sq_threshold(h->w_hab[3 * i + 2]);
+    hab[4 * i + 3] = auvp::sq_threshold(h->w_hab[3 * i + 2]);
   }
   for (size_t i = 0; i < rc.size(); i++) rc[i] = round2_py(h->w_cells[i]);
   std::vector<double> tmp(C);

@@ -12,6 +12,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,7 @@
 #include "planner_goal_arc.h"
 #include "planner_pipe_kernel.h"
 #include "launch_plan.h"  // (behind every kernel header whose LDS plan and limits the choice reads)
+#include "world_tables.h"
 
 using namespace auvp;
 
@@ -187,20 +189,6 @@ void seed_mt(uint64_t seed, uint32_t* mt) {
   mt[0] = 0x80000000u;
 }
 
-// largest double s with RN(sqrt(s)) <= R  (R < 0 -> -1: `d <= size` can never hold)
-double sq_threshold(double R) {
-  if (!(R >= 0.0)) return -1.0;
-  double s = R * R;
-  if (std::isinf(s)) return s;
-  while (std::sqrt(s) > R) s = std::nextafter(s, -INFINITY);
-  for (;;) {
-    double n = std::nextafter(s, INFINITY);
-    if (std::isinf(n) || std::sqrt(n) > R) break;
-    s = n;
-  }
-  return s;
-}
-
 template <class T>
 int upload(auvp_handle* h, DevBuf& b, const T* src, size_t n) {
   HIPCHK(h, b.reserve(n * sizeof(T)));
@@ -208,52 +196,59 @@ int upload(auvp_handle* h, DevBuf& b, const T* src, size_t n) {
   return AUVP_OK;
 }
 
+// one table on its way to HBM: the buffer it gets, the host memory it is copied from
+struct TableUpload {
+  DevBuf& buf;
+  const void* src;
+  size_t bytes;
+  template <class T>
+  TableUpload(DevBuf& b, const std::vector<T>& v) : buf(b), src(v.data()), bytes(v.size() * sizeof(T)) {}
+  TableUpload(DevBuf& b, const double* p, size_t n) : buf(b), src(p), bytes(n * sizeof(double)) {}
+};
 
-// habitat mask grid (auvp_types.h): 32 x 32 cells over the box of the habitats' cull squares; a habitat is entered into
-// every cell its square touches, one cell of margin on each side against rounding in the cell arithmetic
-int build_habitat_grid(auvp_handle* h, const double* habitats, int H) {
-  WorldDev& W = h->W;
-  W.hg_n = 0; W._pad_hg = 0; W.hg_x0 = W.hg_y0 = W.hg_inv_w = W.hg_inv_h = 0.0;
-  W.hg_mask = nullptr;
-  if (H <= 0 || H > 64 || h->opt_on(OPT_NO_HABITAT_GRID)) return AUVP_OK;
-  const int G = 32;
-  double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
-  std::vector<double> rr(H);
-  for (int i = 0; i < H; i++) {
-    const double t = sq_threshold(habitats[3 * i + 2]);
-    rr[i] = t >= 0.0 ? std::sqrt(t) * (1.0 + 0x1p-30) + 0x1p-40 : -1.0;
-    const double hx = habitats[3 * i], hy = habitats[3 * i + 1];
-    if (!std::isfinite(hx) || !std::isfinite(hy) || !std::isfinite(rr[i])) return AUVP_OK;  // odd input: keep the plain scan
-    if (rr[i] < 0.0) continue;  // can never contain a point
-    x0 = std::min(x0, hx - rr[i]); x1 = std::max(x1, hx + rr[i]);
-    y0 = std::min(y0, hy - rr[i]); y1 = std::max(y1, hy + rr[i]);
+// every table of the list, then ONE wait: the host memory behind `src` must live until this returns
+int upload_tables(auvp_handle* h, std::initializer_list<TableUpload> tables) {
+  for (const TableUpload& u : tables) {
+    HIPCHK(h, u.buf.reserve(u.bytes));
+    if (u.bytes) HIPCHK(h, hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, h->stream));
   }
-  std::vector<unsigned long long> mask((size_t)G * G, 0ull);
-  if (x1 >= x0 && y1 >= y0) {
-    // grow the box a little so that every square lies strictly inside it
-    const double mx = 1e-6 * (std::fabs(x0) + std::fabs(x1) + 1.0), my = 1e-6 * (std::fabs(y0) + std::fabs(y1) + 1.0);
-    x0 -= mx; x1 += mx; y0 -= my; y1 += my;
-    const double iw = (double)G / (x1 - x0), ih = (double)G / (y1 - y0);
-    for (int i = 0; i < H; i++) {
-      if (rr[i] < 0.0) continue;
-      const double hx = habitats[3 * i], hy = habitats[3 * i + 1];
-      int cx0 = (int)std::floor((hx - rr[i] - x0) * iw) - 1, cx1 = (int)std::floor((hx + rr[i] - x0) * iw) + 1;
-      int cy0 = (int)std::floor((hy - rr[i] - y0) * ih) - 1, cy1 = (int)std::floor((hy + rr[i] - y0) * ih) + 1;
-      cx0 = std::max(cx0, 0); cy0 = std::max(cy0, 0); cx1 = std::min(cx1, G - 1); cy1 = std::min(cy1, G - 1);
-      for (int cy = cy0; cy <= cy1; cy++)
-        for (int cx = cx0; cx <= cx1; cx++) mask[(size_t)cy * G + cx] |= 1ull << i;
-    }
-    W.hg_x0 = x0; W.hg_y0 = y0; W.hg_inv_w = iw; W.hg_inv_h = ih;
-  } else {
-    W.hg_inv_w = W.hg_inv_h = 0.0;  // no habitat can contain anything: every cell empty (floor(nan/inf) guards below)
-    W.hg_x0 = W.hg_y0 = 0.0;
-  }
-  int rc = upload(h, h->d_hgmask, mask.data(), mask.size());
-  if (rc != AUVP_OK) return rc;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, AUVP_ERR_HIP, "habitat grid upload");
-  W.hg_mask = h->d_hgmask.as<unsigned long long>();
-  W.hg_n = G;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return AUVP_OK;
+}
+
+// the habitats' fields of WorldDev from their tables (world_tables.h) and the buffers these were uploaded to
+void fill_habitat_dev(auvp_handle* h, int H, const HabitatTables& t) {
+  WorldDev& W = h->W;
+  W.n_habitats = H;
+  W.hab = h->d_hab.as<double>(); W.hab_t = h->d_habt.as<double>();
+  W.hg_n = t.hg_n; W._pad_hg = 0;
+  W.hg_x0 = t.hg_x0; W.hg_y0 = t.hg_y0; W.hg_inv_w = t.hg_inv_w; W.hg_inv_h = t.hg_inv_h;
+  W.hg_mask = t.hg_n ? h->d_hgmask.as<unsigned long long>() : nullptr;
+}
+
+// WorldDev from the world's sizes, its tables (world_tables.h) and the buffers these were uploaded to
+void fill_world_dev(auvp_handle* h, const WorldIn& in, const WorldTables& t) {
+  WorldDev& W = h->W;
+  W.n_obstacles = in.O; W.n_poly = in.V; W.n_bins = in.T; W.n_cells = in.C; W.n_xbuckets = t.n_xbuckets;
+  W.ox = h->d_ox.as<double>(); W.oy = h->d_oy.as<double>(); W.ot = h->d_ot.as<double>();
+  W.os_x = h->d_osx.as<double>(); W.os_y = h->d_osy.as<double>(); W.os_t = h->d_ost.as<double>(); W.os_r = h->d_osr.as<float>();
+  W.os_box = h->d_osbox.as<double>();
+  W.poly = h->d_poly.as<double>(); W.bins = h->d_bins.as<double>(); W.cells = h->d_cells.as<double>(); W.prob = h->d_prob.as<double>();
+  W.xb_off = h->d_xoff.as<int32_t>(); W.xb_items = h->d_xitems.as<int32_t>(); W.xb_data = h->d_xdata.as<double>();
+  W.xb_x0 = t.xb_x0; W.xb_inv_w = t.xb_inv_w;
+  W.rg_enabled = t.rg_enabled; W.n_rg_bp = t.n_rg_bp;
+  W.rg_first = h->d_rgfirst.as<int32_t>(); W.rg_bp = h->d_rgbp.as<double>(); W.rg_off = h->d_rgoff.as<int32_t>();
+  W.rg_pm = h->d_rgpm.as<double>(); W.rg_id = h->d_rgid.as<int32_t>();
+  W.sg_enabled = t.sg_enabled; W.sg_ncol = t.sg_ncol; W.sg_nrow = t.sg_nrow;
+  W.sg_x0 = h->d_sgx0.as<double>(); W.sg_x1 = h->d_sgx1.as<double>(); W.sg_y0 = h->d_sgy0.as<double>(); W.sg_y1 = h->d_sgy1.as<double>();
+  W.sg_col = h->d_sgcol.as<double>(); W.sg_row = h->d_sgrow.as<double>();
+  W.sg_x1_0 = t.sg_x1_0; W.sg_y1_0 = t.sg_y1_0; W.sg_inv_dx = t.sg_inv_dx; W.sg_inv_dy = t.sg_inv_dy;
+  W.bins_sorted = t.bins_sorted; W.bins_t1_0 = t.bins_t1_0; W.bins_inv_len = t.bins_inv_len;
+  W.prob_absmax = t.prob_absmax; W.prob_one_sign = t.prob_one_sign; W._pad_prob = 0;
+  memcpy(W.bb, t.bb, sizeof W.bb);
+  memcpy(W.safe_box, t.safe_box, sizeof W.safe_box);
+  W.has_safe_box = t.has_safe_box; W._pad1 = 0;
+  fill_habitat_dev(h, in.H, t.hab);
 }
 
 }  // namespace
@@ -367,279 +362,29 @@ int auvp_world_set(auvp_handle* h, const double* obstacles, int32_t O, const dou
   HIPCHK(h, hipSetDevice(h->device));
   h->n_sets = 0;  // the probability sets belonged to the world that goes (its bins and cells)
   h->grids = false;
-  std::vector<double> ox(O), oy(O), ot(O);
-  double run = -INFINITY;
-  for (int i = O - 1; i >= 0; i--) {  // suffix max of the radii, list order
-    double r = obstacles[3 * i + 2];
-    if (r > run) run = r;
-    ox[i] = obstacles[3 * i];
-    oy[i] = obstacles[3 * i + 1];
-    ot[i] = sq_threshold(run);
-  }
-  // x-bucket index over the cells
-  std::vector<int32_t> xoff, xitems;
-  std::vector<double> xdata;
-  double X0 = 0.0, inv_w = 0.0;
-  int NB = 0;
-  if (C > 0) {
-    double lo = INFINITY, hi = -INFINITY, wmin = INFINITY;
-    for (int c = 0; c < C; c++) {
-      double a = cells[4 * c], b = std::min(cells[4 * c + 2], cells[4 * c + 3]);
-      double wdt = cells[4 * c + 2] - cells[4 * c];
-      if (wdt > 0 && wdt < wmin) wmin = wdt;
-      if (b < a) continue;
-      lo = std::min(lo, a);
-      hi = std::max(hi, b);
-    }
-    if (!(hi >= lo)) { lo = 0.0; hi = 1.0; }
-    double span = hi - lo;
-    NB = 1;
-    if (span > 0 && std::isfinite(wmin)) NB = (int)std::min(8192.0, std::max(1.0, std::ceil(span / wmin)));
-    X0 = lo;
-    inv_w = span > 0 ? (double)NB / span : 0.0;
-    std::vector<std::vector<int32_t>> lists(NB);
-    for (int c = 0; c < C; c++) {
-      double a = cells[4 * c], b = std::min(cells[4 * c + 2], cells[4 * c + 3]);
-      if (b < a) continue;
-      int b0 = (int)std::floor((a - X0) * inv_w) - 1, b1 = (int)std::floor((b - X0) * inv_w) + 1;
-      b0 = std::max(0, std::min(NB - 1, b0));
-      b1 = std::max(0, std::min(NB - 1, b1));
-      for (int k = b0; k <= b1; k++) lists[k].push_back(c);
-    }
-    xoff.resize(NB + 1);
-    xoff[0] = 0;
-    for (int k = 0; k < NB; k++) {
-      xoff[k + 1] = xoff[k] + (int32_t)lists[k].size();
-      xitems.insert(xitems.end(), lists[k].begin(), lists[k].end());
-    }
-    xdata.resize(xitems.size() * 4);
-    for (int k = 0; k < NB; k++) {
-      double suf = INFINITY;
-      for (int i = xoff[k + 1] - 1; i >= xoff[k]; i--) {
-        const double* cb = cells + 4 * (size_t)xitems[i];
-        suf = std::min(suf, cb[1]);
-        xdata[4 * (size_t)i] = cb[0];
-        xdata[4 * (size_t)i + 1] = std::min(cb[2], cb[3]);
-        xdata[4 * (size_t)i + 2] = cb[1];
-        xdata[4 * (size_t)i + 3] = suf;
-      }
-    }
-  } else {
-    xoff.assign(2, 0);
-  }
-  // region index (auvp_types.h): breakpoints, per-region candidate lists with running min of miny
-  std::vector<double> bp, rpm;
-  std::vector<int32_t> rfirst(NB + 1, 0), roff(2, 0), rid;
-  int rg_enabled = 0;
-  if (C > 0) {
-    bp.reserve((size_t)2 * C);
-    for (int c = 0; c < C; c++) {
-      const double a = cells[4 * c], b = std::min(cells[4 * c + 2], cells[4 * c + 3]);
-      if (b < a || a != a || b != b) continue;
-      bp.push_back(a); bp.push_back(b);
-    }
-    std::sort(bp.begin(), bp.end());
-    bp.erase(std::unique(bp.begin(), bp.end()), bp.end());
-    const size_t m = bp.size();
-    auto bucket_of = [&](double x) {
-      const double fb = std::floor((x - X0) * inv_w);
-      return fb < 0.0 ? 0 : (fb >= (double)NB ? NB - 1 : (int)fb);
-    };
-    for (size_t i = 0; i < m; i++) rfirst[bucket_of(bp[i]) + 1]++;
-    for (int k = 0; k < NB; k++) rfirst[k + 1] += rfirst[k];
-    const size_t R = 2 * m + 1;
-    std::vector<int64_t> cnt(R + 1, 0);
-    std::vector<int32_t> r0(C, 0), r1(C, -1);
-    for (int c = 0; c < C; c++) {
-      const double a = cells[4 * c], b = std::min(cells[4 * c + 2], cells[4 * c + 3]);
-      if (b < a || a != a || b != b) continue;
-      r0[c] = 2 * (int32_t)(std::lower_bound(bp.begin(), bp.end(), a) - bp.begin()) + 1;
-      r1[c] = 2 * (int32_t)(std::lower_bound(bp.begin(), bp.end(), b) - bp.begin()) + 1;
-      cnt[r0[c]]++; cnt[r1[c] + 1]--;
-    }
-    int64_t total = 0, run = 0;
-    for (size_t r = 0; r < R; r++) { run += cnt[r]; total += run; }
-    int64_t budget = 32ll << 20;
-    budget = h->opt_num(OPT_RG_MAX_ENTRIES, budget);
-    if (total <= budget && R + 1 < (size_t)INT32_MAX) {
-      rg_enabled = 1;
-      roff.assign(R + 1, 0);
-      run = 0;
-      for (size_t r = 0; r < R; r++) { run += cnt[r]; roff[r + 1] = roff[r] + (int32_t)run; }
-      rpm.resize((size_t)total); rid.resize((size_t)total);
-      std::vector<int32_t> fill(roff.begin(), roff.end() - 1);
-      for (int c = 0; c < C; c++)
-        for (int32_t r = r0[c]; r <= r1[c]; r++) {
-          const int32_t k = fill[r]++;
-          rid[k] = c;
-          rpm[k] = (k > roff[r]) ? std::min(rpm[k - 1], cells[4 * c + 1]) : cells[4 * c + 1];
-        }
-    } else {
-      bp.clear();
-      std::fill(rfirst.begin(), rfirst.end(), 0);
-    }
-  }
-  // separable-grid index (auvp_types.h): cell_list row-major over non-decreasing X0/X1 (columns) and Y0/Y1 (rows)
-  std::vector<double> sgx0, sgx1, sgy0, sgy1;
-  int sg_ncol = 0, sg_nrow = 0;
-  if (C > 0) {
-    int nc = 1;
-    while (nc < C && cells[4 * (size_t)nc + 1] == cells[1] && cells[4 * (size_t)nc + 3] == cells[3]) nc++;
-    if (C % nc == 0) {
-      const int nr = C / nc;
-      bool ok = true;
-      sgx0.resize(nc); sgx1.resize(nc); sgy0.resize(nr); sgy1.resize(nr);
-      for (int c = 0; c < nc; c++) { sgx0[c] = cells[4 * (size_t)c]; sgx1[c] = cells[4 * (size_t)c + 2]; }
-      for (int r = 0; r < nr; r++) { sgy0[r] = cells[4 * (size_t)r * nc + 1]; sgy1[r] = cells[4 * (size_t)r * nc + 3]; }
-      for (int r = 0; r < nr && ok; r++)
-        for (int c = 0; c < nc; c++) {
-          const double* cb = cells + 4 * ((size_t)r * nc + c);
-          if (!(cb[0] == sgx0[c] && cb[1] == sgy0[r] && cb[2] == sgx1[c] && cb[3] == sgy1[r])) { ok = false; break; }
-        }
-      for (int c = 1; c < nc && ok; c++) ok = sgx0[c] >= sgx0[c - 1] && sgx1[c] >= sgx1[c - 1];
-      for (int r = 1; r < nr && ok; r++) ok = sgy0[r] >= sgy0[r - 1] && sgy1[r] >= sgy1[r - 1];
-      for (int c = 0; c < nc && ok; c++) ok = std::isfinite(sgx0[c]) && std::isfinite(sgx1[c]);
-      for (int r = 0; r < nr && ok; r++) ok = std::isfinite(sgy0[r]) && std::isfinite(sgy1[r]);
-      if (ok && !h->opt_on(OPT_NO_GRID_INDEX)) { sg_ncol = nc; sg_nrow = nr; }
-    }
-  }
-  double prob_absmax = 0.0;
-  bool any_pos = false, any_neg = false, any_nan = false;
-  for (size_t i = 0; i < (size_t)T * C; i++) {
-    const double a = std::fabs(prob[i]);
-    if (a > prob_absmax || a != a) prob_absmax = a;  // a nan poisons the bound: every leaf is then re-summed exactly
-    any_pos |= prob[i] > 0; any_neg |= prob[i] < 0; any_nan |= prob[i] != prob[i];
-  }
-  int rc;
-  if ((rc = upload(h, h->d_rgfirst, rfirst.data(), rfirst.size()))) return rc;
-  if ((rc = upload(h, h->d_rgbp, bp.data(), bp.size()))) return rc;
-  if ((rc = upload(h, h->d_rgoff, roff.data(), roff.size()))) return rc;
-  if ((rc = upload(h, h->d_rgpm, rpm.data(), rpm.size()))) return rc;
-  if ((rc = upload(h, h->d_rgid, rid.data(), rid.size()))) return rc;
-  if ((rc = upload(h, h->d_sgx0, sgx0.data(), (size_t)sg_ncol))) return rc;
-  if ((rc = upload(h, h->d_sgx1, sgx1.data(), (size_t)sg_ncol))) return rc;
-  if ((rc = upload(h, h->d_sgy0, sgy0.data(), (size_t)sg_nrow))) return rc;
-  if ((rc = upload(h, h->d_sgy1, sgy1.data(), (size_t)sg_nrow))) return rc;
-  {
-    std::vector<double> col((size_t)sg_ncol * 4, 0.0), row((size_t)sg_nrow * 4, 0.0);
-    for (int c = 0; c < sg_ncol; c++) { col[4 * (size_t)c] = c ? sgx1[c - 1] : -INFINITY; col[4 * (size_t)c + 1] = sgx1[c]; col[4 * (size_t)c + 2] = sgx0[c]; }
-    for (int r = 0; r < sg_nrow; r++) { row[4 * (size_t)r] = r ? sgy1[r - 1] : -INFINITY; row[4 * (size_t)r + 1] = sgy1[r]; row[4 * (size_t)r + 2] = sgy0[r]; }
-    if ((rc = upload(h, h->d_sgcol, col.data(), col.size()))) return rc;
-    if ((rc = upload(h, h->d_sgrow, row.data(), row.size()))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  {
-    // spatially sorted obstacle tile + slot boxes for rrt_rows_kernel (auvp_types.h)
-    const int NS = 256;
-    std::vector<double> sx(NS, 0.0), sy(NS, 0.0), st(NS, -1.0), box(16 * 4);
-    std::vector<float> sr(NS, -INFINITY);
-    double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;  // bounding box of the obstacle centres
-    for (int i = 0; i < O; i++) { x0 = std::min(x0, ox[i]); x1 = std::max(x1, ox[i]); y0 = std::min(y0, oy[i]); y1 = std::max(y1, oy[i]); }
-    h->obst_area = (O > 1 && std::isfinite((x1 - x0) * (y1 - y0))) ? (x1 - x0) * (y1 - y0) : 0.0;
-    if (O <= NS) {
-      auto spread = [](uint32_t v) { uint64_t x = v & 0xffff; x = (x | (x << 8)) & 0x00ff00ff; x = (x | (x << 4)) & 0x0f0f0f0f;
-                                     x = (x | (x << 2)) & 0x33333333; x = (x | (x << 1)) & 0x55555555; return x; };
-      std::vector<std::pair<uint64_t, int>> key(O);
-      for (int i = 0; i < O; i++) {
-        const double fx = x1 > x0 ? (ox[i] - x0) / (x1 - x0) : 0.0, fy = y1 > y0 ? (oy[i] - y0) / (y1 - y0) : 0.0;
-        const uint32_t qx = (uint32_t)std::min(65535.0, std::max(0.0, fx * 65535.0)), qy = (uint32_t)std::min(65535.0, std::max(0.0, fy * 65535.0));
-        key[i] = {(std::isfinite(fx) && std::isfinite(fy)) ? (spread(qx) | (spread(qy) << 1)) : 0, i};
-      }
-      std::sort(key.begin(), key.end());
-      for (int k = 0; k < O; k++) {
-        const int i = key[k].second;
-        sx[k] = ox[i]; sy[k] = oy[i]; st[k] = ot[i];
-        const double rd = ot[i] >= 0.0 ? std::sqrt(ot[i]) * (1.0 + 0x1p-30) + 0x1p-40 : -INFINITY;
-        float rf = (float)rd;
-        if ((double)rf < rd) rf = std::nextafter(rf, INFINITY);
-        sr[k] = rf;
-      }
-    }
-    for (int s_ = 0; s_ < 16; s_++) {
-      double b0 = INFINITY, b1 = INFINITY, b2 = -INFINITY, b3 = -INFINITY;
-      for (int k = 16 * s_; k < 16 * s_ + 16; k++) {
-        if (!(sr[k] >= 0.0f) && !std::isnan(sx[k])) continue;  // padding / an obstacle that can never collide
-        const double r = (double)sr[k];
-        if (std::isnan(sx[k]) || std::isnan(sy[k]) || std::isnan(r)) { b0 = b1 = -INFINITY; b2 = b3 = INFINITY; break; }  // never culled
-        b0 = std::min(b0, sx[k] - r); b1 = std::min(b1, sy[k] - r); b2 = std::max(b2, sx[k] + r); b3 = std::max(b3, sy[k] + r);
-      }
-      box[4 * s_] = b0; box[4 * s_ + 1] = b1; box[4 * s_ + 2] = b2; box[4 * s_ + 3] = b3;
-    }
-    int rc2;
-    if ((rc2 = upload(h, h->d_osx, sx.data(), sx.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_osy, sy.data(), sy.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_ost, st.data(), st.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_osr, sr.data(), sr.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_osbox, box.data(), box.size()))) return rc2;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  if ((rc = upload(h, h->d_ox, ox.data(), O))) return rc;
-  if ((rc = upload(h, h->d_oy, oy.data(), O))) return rc;
-  if ((rc = upload(h, h->d_ot, ot.data(), O))) return rc;
-  if ((rc = upload(h, h->d_hab, habitats, (size_t)H * 3))) return rc;
-  {
-    std::vector<double> ht(H);
-    for (int i = 0; i < H; i++) ht[i] = sq_threshold(habitats[3 * i + 2]);
-    if ((rc = upload(h, h->d_habt, ht.data(), (size_t)H))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  if ((rc = upload(h, h->d_poly, polygon, (size_t)V * 2))) return rc;
-  if ((rc = upload(h, h->d_bins, bins, (size_t)T * 2))) return rc;
-  if ((rc = upload(h, h->d_cells, cells, (size_t)C * 4))) return rc;
-  if ((rc = upload(h, h->d_prob, prob, (size_t)T * C))) return rc;
-  if ((rc = upload(h, h->d_xoff, xoff.data(), xoff.size()))) return rc;
-  if ((rc = upload(h, h->d_xitems, xitems.data(), xitems.size()))) return rc;
-  if ((rc = upload(h, h->d_xdata, xdata.data(), xdata.size()))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
-  WorldDev& W = h->W;
-  W.n_obstacles = O; W.n_habitats = H; W.n_poly = V; W.n_bins = T; W.n_cells = C; W.n_xbuckets = NB;
-  W.ox = h->d_ox.as<double>(); W.oy = h->d_oy.as<double>(); W.ot = h->d_ot.as<double>();
-  W.os_x = h->d_osx.as<double>(); W.os_y = h->d_osy.as<double>(); W.os_t = h->d_ost.as<double>(); W.os_r = h->d_osr.as<float>();
-  W.os_box = h->d_osbox.as<double>();
-  W.hab = h->d_hab.as<double>(); W.hab_t = h->d_habt.as<double>(); W.poly = h->d_poly.as<double>(); W.bins = h->d_bins.as<double>();
-  W.cells = h->d_cells.as<double>(); W.prob = h->d_prob.as<double>();
-  W.xb_off = h->d_xoff.as<int32_t>(); W.xb_items = h->d_xitems.as<int32_t>(); W.xb_data = h->d_xdata.as<double>();
-  W.xb_x0 = X0; W.xb_inv_w = inv_w;
-  W.rg_enabled = rg_enabled; W.n_rg_bp = (int32_t)bp.size();
-  W.rg_first = h->d_rgfirst.as<int32_t>(); W.rg_bp = h->d_rgbp.as<double>(); W.rg_off = h->d_rgoff.as<int32_t>();
-  W.rg_pm = h->d_rgpm.as<double>(); W.rg_id = h->d_rgid.as<int32_t>();
-  W.sg_enabled = sg_ncol > 0 ? 1 : 0; W.sg_ncol = sg_ncol; W.sg_nrow = sg_nrow;
-  W.sg_col = h->d_sgcol.as<double>(); W.sg_row = h->d_sgrow.as<double>();
-  W.sg_x1_0 = sg_ncol > 0 ? sgx1[0] : 0.0; W.sg_y1_0 = sg_nrow > 0 ? sgy1[0] : 0.0;
-  {
-    bool sorted = T > 0;
-    for (int t = 0; t < T && sorted; t++) sorted = std::isfinite(bins[2 * t]) && std::isfinite(bins[2 * t + 1]);
-    for (int t = 1; t < T && sorted; t++) sorted = bins[2 * t] >= bins[2 * (t - 1)] && bins[2 * t + 1] >= bins[2 * (t - 1) + 1];
-    W.bins_sorted = sorted ? 1 : 0;
-    W.bins_t1_0 = T > 0 ? bins[1] : 0.0;
-    W.bins_inv_len = (sorted && T > 1 && bins[2 * (T - 1) + 1] > bins[1]) ? (double)(T - 1) / (bins[2 * (T - 1) + 1] - bins[1]) : 0.0;
-  }
-  W.sg_x0 = h->d_sgx0.as<double>(); W.sg_x1 = h->d_sgx1.as<double>(); W.sg_y0 = h->d_sgy0.as<double>(); W.sg_y1 = h->d_sgy1.as<double>();
-  W.sg_inv_dx = (sg_ncol > 1 && sgx1[sg_ncol - 1] > sgx1[0]) ? (double)(sg_ncol - 1) / (sgx1[sg_ncol - 1] - sgx1[0]) : 0.0;
-  W.sg_inv_dy = (sg_nrow > 1 && sgy1[sg_nrow - 1] > sgy1[0]) ? (double)(sg_nrow - 1) / (sgy1[sg_nrow - 1] - sgy1[0]) : 0.0;
-  W.prob_absmax = prob_absmax;
-  W.prob_one_sign = (!any_nan && !(any_pos && any_neg)) ? 1 : 0;
-  W._pad_prob = 0;
-  if ((rc = build_habitat_grid(h, habitats, H))) return rc;
-  double bb[4] = {INFINITY, INFINITY, -INFINITY, -INFINITY};
-  for (int i = 0; i < V; i++) {
-    bb[0] = std::min(bb[0], polygon[2 * i]); bb[1] = std::min(bb[1], polygon[2 * i + 1]);
-    bb[2] = std::max(bb[2], polygon[2 * i]); bb[3] = std::max(bb[3], polygon[2 * i + 1]);
-  }
-  memcpy(W.bb, bb, sizeof bb);
-  // axis-aligned rectangle given by its 4 corners: strict containment in it implies Point.within
-  W.has_safe_box = 0;
-  if (V == 4) {
-    bool rect = true;
-    for (int i = 0; i < 4 && rect; i++) {
-      const double x0 = polygon[2 * i], y0 = polygon[2 * i + 1], x1 = polygon[2 * ((i + 1) % 4)], y1 = polygon[2 * ((i + 1) % 4) + 1];
-      const bool horiz = (y0 == y1) && (x0 != x1), vert = (x0 == x1) && (y0 != y1);
-      const double x2 = polygon[2 * ((i + 2) % 4)], y2 = polygon[2 * ((i + 2) % 4) + 1];
-      const bool next_vert = (x1 == x2) && (y1 != y2), next_horiz = (y1 == y2) && (x1 != x2);
-      rect = (horiz && next_vert) || (vert && next_horiz);
-    }
-    if (rect) { W.has_safe_box = 1; memcpy(W.safe_box, bb, sizeof bb); }
-  }
+  WorldIn in;
+  in.obstacles = obstacles; in.O = O; in.habitats = habitats; in.H = H; in.polygon = polygon; in.V = V;
+  in.bins = bins; in.T = T; in.cells = cells; in.C = C; in.prob = prob;
+  in.rg_max_entries = h->opt_num(OPT_RG_MAX_ENTRIES, in.rg_max_entries);
+  in.grid_index = !h->opt_on(OPT_NO_GRID_INDEX);
+  in.habitat_grid = !h->opt_on(OPT_NO_HABITAT_GRID);
+  const WorldTables t = build_world_tables(in);
+  // a buffer that grows is released first (DevBuf::reserve): from here to the end WorldDev may point into freed memory
+  h->have_world = false;
+  int rc = upload_tables(h, {
+      {h->d_ox, t.ox}, {h->d_oy, t.oy}, {h->d_ot, t.ot},
+      {h->d_osx, t.os_x}, {h->d_osy, t.os_y}, {h->d_ost, t.os_t}, {h->d_osr, t.os_r}, {h->d_osbox, t.os_box},
+      {h->d_hab, habitats, (size_t)H * 3}, {h->d_habt, t.hab.hab_t}, {h->d_hgmask, t.hab.hg_mask},
+      {h->d_poly, polygon, (size_t)V * 2}, {h->d_bins, bins, (size_t)T * 2}, {h->d_cells, cells, (size_t)C * 4},
+      {h->d_prob, prob, (size_t)T * C},
+      {h->d_xoff, t.xb_off}, {h->d_xitems, t.xb_items}, {h->d_xdata, t.xb_data},
+      {h->d_rgfirst, t.rg_first}, {h->d_rgbp, t.rg_bp}, {h->d_rgoff, t.rg_off}, {h->d_rgpm, t.rg_pm}, {h->d_rgid, t.rg_id},
+      {h->d_sgx0, t.sg_x0}, {h->d_sgx1, t.sg_x1}, {h->d_sgy0, t.sg_y0}, {h->d_sgy1, t.sg_y1},
+      {h->d_sgcol, t.sg_col}, {h->d_sgrow, t.sg_row},
+  });
+  if (rc != AUVP_OK) return rc;
+  fill_world_dev(h, in, t);
+  h->obst_area = t.obst_area;
   // host copies: the A* family derives its own device tables from the same world (astar_host.h)
   h->w_obst.assign(obstacles, obstacles + (size_t)O * 3);
   h->w_hab.assign(habitats, habitats + (size_t)H * 3);
@@ -657,16 +402,12 @@ int auvp_world_set_habitats(auvp_handle* h, const double* habitats, int32_t H) {
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   if (H < 0 || H > RRT_MAX_HAB) return fail(h, AUVP_ERR_ARG, "n_habitats %d outside 0..%d", H, RRT_MAX_HAB);
   HIPCHK(h, hipSetDevice(h->device));
-  int rc;
-  if ((rc = upload(h, h->d_hab, habitats, (size_t)H * 3))) return rc;
-  std::vector<double> ht(H);
-  for (int i = 0; i < H; i++) ht[i] = sq_threshold(habitats[3 * i + 2]);
-  if ((rc = upload(h, h->d_habt, ht.data(), (size_t)H))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->W.n_habitats = H;
-  h->W.hab = h->d_hab.as<double>();
-  h->W.hab_t = h->d_habt.as<double>();
-  if ((rc = build_habitat_grid(h, habitats, H))) return rc;
+  const HabitatTables t = build_habitat_tables(habitats, H, !h->opt_on(OPT_NO_HABITAT_GRID));
+  // no habitat and no grid until the new tables are in place (a buffer that grows is released first)
+  h->W.n_habitats = 0; h->W.hg_n = 0;
+  int rc = upload_tables(h, {{h->d_hab, habitats, (size_t)H * 3}, {h->d_habt, t.hab_t}, {h->d_hgmask, t.hg_mask}});
+  if (rc != AUVP_OK) return rc;
+  fill_habitat_dev(h, H, t);
   h->w_hab.assign(habitats, habitats + (size_t)H * 3);
   h->world_version++;
   return AUVP_OK;

@@ -112,7 +112,7 @@ def test_astar_without_obstacles(ctx, orc):
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
-def test_cell_lookup_index_is_exact_for_arbitrary_cell_lists(ctx, orc, seed, monkeypatch):
+def test_cell_lookup_index_is_exact_for_arbitrary_cell_lists(ctx, orc, seed):
     """cost.py:181-184 first-match scan (with its `x <= maxy` comparison) over cell lists that are NOT grids:
     overlapping rectangles in random order, degenerate cells, query points exactly on minx / maxx / maxy values.
     The region index (default), the bucket scan (index budget forced to 0) and the CPU checker must agree bit
@@ -148,13 +148,58 @@ def test_cell_lookup_index_is_exact_for_arbitrary_cell_lists(ctx, orc, seed, mon
     want = np.array([orc.cost(w, lo, hi, p, tt, ww, kind="portable") for p, lo, hi, tt, ww in zip(paths, los, his, tots, ws)])
     ctx.set_world(None, habitats, None, bins, cells, prob)
     got_index = ctx.cost_paths(paths, los, his, tots, ws)
-    monkeypatch.setenv("AUVP_RG_MAX_ENTRIES", "0")
-    ctx.set_world(None, habitats, None, bins, cells, prob)
-    got_scan = ctx.cost_paths(paths, los, his, tots, ws)
-    monkeypatch.delenv("AUVP_RG_MAX_ENTRIES")
+    ctx.set_option("RG_MAX_ENTRIES", 0)   # (an option of the handle: the environment is only read when a handle is created)
+    try:
+        assert ctx.get_option("RG_MAX_ENTRIES") == 0
+        ctx.set_world(None, habitats, None, bins, cells, prob)
+        got_scan = ctx.cost_paths(paths, los, his, tots, ws)
+    finally:
+        ctx.set_option("RG_MAX_ENTRIES", None)
     assert np.array_equal(got_index, want)
     assert np.array_equal(got_scan, want)
     assert (want[:, 3] != 0).sum() > 10
+
+
+def test_cell_lookup_on_a_grid_is_the_same_through_every_index(ctx, orc):
+    """a row-major grid of cells, points on and off the cells' edges and outside the grid: the separable-grid index (default),
+    the region index (NO_GRID_INDEX) and the bucket scan (NO_GRID_INDEX and no entry budget) against the CPU checker, bit for
+    bit.  (The tables themselves: tests/test_world_tables.py.)"""
+    from auv_sim_amd import synth
+    world = synth.make_world(seed=1, n_obstacles=64)
+    habitats, bins, cells, prob = world["habitats"], world["bins"], world["cells"], world["prob"]
+    T = len(bins)
+    rng = np.random.default_rng(9)
+    edges = np.concatenate([cells[:, 0], cells[:, 2], cells[:, 3]])
+    paths, los, his, tots, ws = [], [], [], [], []
+    for _ in range(40):
+        n = int(rng.integers(1, 150))
+        # x is compared with the rows' maxy as well as with the columns (cost.py:182): both extents, and beyond
+        x = np.where(rng.random(n) < 0.6, rng.uniform(-330.0, -70.0, n), rng.uniform(-130.0, 130.0, n))
+        on = rng.random(n) < 0.4
+        x[on] = rng.choice(edges, on.sum())
+        y = rng.uniform(-130.0, 130.0, n)
+        yon = rng.random(n) < 0.2
+        y[yon] = rng.choice(cells[:, 1], yon.sum())
+        paths.append(np.stack([x, y, rng.uniform(-10.0, 520.0, n)], axis=1))
+        lo = int(rng.integers(0, T))
+        los.append(lo)
+        his.append(int(rng.integers(lo, T + 1)))
+        tots.append(float(rng.choice([0.0, 37.5, 200.0])))
+        ws.append([-3.0, -3.0, -4.0])
+    w = orc.WorldArrays(None, habitats, None, bins, cells, prob)
+    want = np.array([orc.cost(w, lo, hi, p, tt, ww, kind="portable") for p, lo, hi, tt, ww in zip(paths, los, his, tots, ws)])
+    assert (want[:, 3] != 0).sum() > 10
+    for opts in ({}, {"NO_GRID_INDEX": 1}, {"NO_GRID_INDEX": 1, "RG_MAX_ENTRIES": 0}):
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        try:
+            assert all(ctx.get_option(k) == v for k, v in opts.items())
+            ctx.set_world(None, habitats, None, bins, cells, prob)
+            got = ctx.cost_paths(paths, los, his, tots, ws)
+        finally:
+            for k in opts:
+                ctx.set_option(k, None)
+        assert np.array_equal(got, want), opts
 
 
 def test_exploring_with_unordered_overlapping_bins(ctx, orc):
