@@ -33,12 +33,37 @@ def _bind():
     L.auvp_astar_hab_left.argtypes = [vp, C.c_int32, _ip]
     L.auvp_astar_set_visited.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
     L.auvp_astar_get_visited.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint8)]
+    if hasattr(L, "auvp_astar_batch_sets"):  # (an earlier build loaded through AUVPLAN_LIBRARY for a comparison has neither)
+        L.auvp_astar_batch_sets.argtypes = [vp, C.c_int32, _dp, _dp, C.POINTER(AstarParams), C.c_int32, _ip]
+        L.auvp_astar_sets_topn.argtypes = [vp, _dp]
     _bound = True
     return L
 
 
+def sets_topn(ctx):
+    """[G, T, C + 1]: the top-n tables of ctx's probability sets as the searches read them (auvp_astar_sets_topn)"""
+    L = _bind()
+    out = np.zeros((max(ctx.n_prob_sets, 1), ctx.world_sizes.get("T", 0), ctx.world_sizes.get("C", 0) + 1))
+    ctx._chk(L.auvp_astar_sets_topn(ctx.h, _lib._p(out)))
+    return out[:ctx.n_prob_sets]
+
+
+def _launch(L, ctx, E, starts, g, lim, p, flags, set_of):
+    """auvp_astar_batch, or auvp_astar_batch_sets with set_of [E]: instance e against probability set set_of[e]"""
+    if set_of is None:
+        return ctx._chk(L.auvp_astar_batch(ctx.h, E, _lib._p(starts), _lib._p(g) if g is not None else None,
+                                           _lib._p(lim) if lim is not None else None, C.byref(p), flags))
+    so = np.ascontiguousarray(np.asarray(set_of, dtype=np.int32).reshape(-1))
+    if len(so) != E:
+        raise ValueError("set_of has %d entries, expected %d" % (len(so), E))
+    if g is not None:
+        raise ValueError("set_of is astar_fixLenSOG's: no goals")
+    return ctx._chk(L.auvp_astar_batch_sets(ctx.h, E, _lib._p(starts), _lib._p(lim) if lim is not None else None, C.byref(p), flags,
+                                            _lib._p(so, _ip)))
+
+
 def run_batch_arrays(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), velocity=1.0, weights=(0, 0, 0, 0),
-                     cap_nodes=20000):
+                     cap_nodes=20000, set_of=None):
     """E searches in one launch + one path-extraction launch; results as arrays (no per-instance Python work):
     summaries [E], offsets [E+1] and the concatenated path / cost_list / node_path / smooth_path rows."""
     L = _bind()
@@ -52,8 +77,7 @@ def run_batch_arrays(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0
         p.w[i] = float(wts[i])
     g = _lib._f64(goals, (-1, 2)) if goals is not None else None
     lim = _lib._f64(limits).reshape(E) if limits is not None else None
-    ctx._chk(L.auvp_astar_batch(ctx.h, E, _lib._p(starts), _lib._p(g) if g is not None else None,
-                                _lib._p(lim) if lim is not None else None, C.byref(p), 0))
+    _launch(L, ctx, E, starts, g, lim, p, 0, set_of)
     batch_ms = ctx.last_kernel_ms()
     summ = np.zeros(E, dtype=ASTAR_SUMMARY_DTYPE)
     ctx._chk(L.auvp_astar_summaries(ctx.h, summ.ctypes.data_as(C.c_void_p)))
@@ -68,8 +92,10 @@ def run_batch_arrays(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0
 
 
 def run_batch(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), velocity=1.0, weights=(0, 0, 0, 0),
-              cap_nodes=20000, exp_log=False, visited=None):
-    """E searches over ctx's world in one launch.  Returns a list of per-instance dicts."""
+              cap_nodes=20000, exp_log=False, visited=None, set_of=None, return_visited=False):
+    """E searches over ctx's world in one launch.  Returns a list of per-instance dicts.  set_of [E] (astar_fixLenSOG): instance e
+    reads the shark-occupancy table and its top-n table of ctx's probability set set_of[e] (Context.set_prob_sets).
+    return_visited: "visited" (the fixLen variants' bitmap after the search) also without a bitmap carried in."""
     L = _bind()
     starts = _lib._f64(starts, (-1, 2))
     E = len(starts)
@@ -86,8 +112,7 @@ def run_batch(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), v
         vis = np.ascontiguousarray(visited, dtype=np.uint8)
         ctx._chk(L.auvp_astar_set_visited(ctx.h, E, p.variant, vis.ctypes.data_as(C.POINTER(C.c_uint8))))
         flags |= 8
-    ctx._chk(L.auvp_astar_batch(ctx.h, E, _lib._p(starts), _lib._p(g) if g is not None else None,
-                                _lib._p(lim) if lim is not None else None, C.byref(p), flags))
+    _launch(L, ctx, E, starts, g, lim, p, flags, set_of)
     summ = np.zeros(E, dtype=ASTAR_SUMMARY_DTYPE)
     ctx._chk(L.auvp_astar_summaries(ctx.h, summ.ctypes.data_as(C.c_void_p)))
     lens = np.where(summ["found"] != 0, summ["path_len"], 0).astype(np.int64)
@@ -111,7 +136,7 @@ def run_batch(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), v
         if H:
             ctx._chk(L.auvp_astar_hab_left(ctx.h, e, _lib._p(hl, _ip)))
         r["hab_left"] = hl[:int(s["n_hab_left"])]
-        if p.variant >= 2 and visited is not None:
+        if p.variant >= 2 and (visited is not None or return_visited):
             vb = np.zeros((550 if p.variant == 2 else 600, 600), dtype=np.uint8)
             ctx._chk(L.auvp_astar_get_visited(ctx.h, e, vb.ctypes.data_as(C.POINTER(C.c_uint8))))
             r["visited"] = vb

@@ -326,6 +326,7 @@ class Context:
         self.max_iter = 0
         self.world_sizes = {}
         self.n_prob_sets = 0
+        self._world_stamp = 0  # counts set_world / set_habitats: a user that shares the context sees whether its world still stands
 
     def close(self):
         if getattr(self, "h", None):
@@ -373,6 +374,7 @@ class Context:
         pr = _f64(prob if prob is not None else [])
         if pr.size != len(bn) * len(ce):
             raise ValueError("prob must be [n_bins, n_cells]")
+        self._world_stamp += 1
         self._chk(self.L.auvp_world_set(self.h, _p(ob), len(ob), _p(hb), len(hb), _p(pg), len(pg), _p(bn), len(bn),
                                         _p(ce), len(ce), _p(pr)))
         self.world_sizes = dict(O=len(ob), H=len(hb), V=len(pg), T=len(bn), C=len(ce))
@@ -380,6 +382,7 @@ class Context:
 
     def set_habitats(self, habitats):
         hb = _f64(habitats if habitats is not None else [], (-1, 3))
+        self._world_stamp += 1
         self._chk(self.L.auvp_world_set_habitats(self.h, _p(hb), len(hb)))
         self.world_sizes["H"] = len(hb)
 

@@ -5,13 +5,18 @@ sharkGrid, shark_dict, AUV_velocity).astar(pathLenLimit, weights, shark_traj)` -
 (:127-132: `cell_list = splitCell(boundary_poly, 10)`, then createSharkGrid on a CSV path relative to its repo root) needs
 shapely for the split; here the caller passes that cell list and the CSV path (`cell_list=`, `shark_csv=`, additive) and the
 module's own createSharkGrid loads it the way the reference's does.  `self.visited_nodes` persists across calls, as in the
-reference."""
+reference.
+
+Beyond the reference (additive): `set_shark_grids(grids)` puts one shark-occupancy table per tracked shark on the planner --
+RRT.set_shark_grids' contract, a `sharkForecast.Forecast` included -- and `astar_batch(..., shark_of=[...])` searches instance i
+against table shark_of[i], probabilities and top-n heuristic alike, in the same launch.  `device_context=`: the `_lib.Context` to
+run on (the forecast's, so that its tables reach the planner without leaving HBM)."""
 import numpy as np
 
 from . import _astar_common as ac
 from ._astar_common import Node
 from .motion_plan_state import Motion_plan_state
-from .rrt_dubins import pack_shark_grid
+from .rrt_dubins import pack_shark_grid, put_shark_tables, shark_set_indices
 
 
 def createSharkGrid(filepath, cell_list):
@@ -32,7 +37,7 @@ def createSharkGrid(filepath, cell_list):
 
 class astar:
     def __init__(self, start, obstacleList, boundaryList, habitatList, sharkGrid, shark_dict, AUV_velocity,
-                 cap_nodes=200000, device=0, cell_list=None, shark_csv=None):
+                 cap_nodes=200000, device=0, cell_list=None, shark_csv=None, device_context=None):
         if not sharkGrid:
             if cell_list is None or shark_csv is None:
                 raise ValueError("sharkGrid is empty: pass cell_list= (the reference's splitCell(boundary_poly, 10)) and shark_csv= "
@@ -48,8 +53,35 @@ class astar:
         self.sharkGrid = sharkGrid
         self.sharkDict = shark_dict
         self.cap_nodes = cap_nodes
-        self._ctx = ac.context(device)
+        self._ctx = device_context if device_context is not None else ac.context(device)
         self._bins, self._cells, self._prob = pack_shark_grid(sharkGrid)
+        self._world = None      # the arrays of the last set_world of astar_batch on self._ctx (None: none yet)
+        self._set_prob = None   # host copy [G, T, C] of the shark tables of set_shark_grids (None: none)
+
+    @property
+    def n_shark_sets(self):
+        return 0 if self._set_prob is None else len(self._set_prob)
+
+    def set_shark_grids(self, grids):
+        """One shark-occupancy table per tracked shark, for astar_batch's shark_of: a list of sharkGrid dicts with the
+        constructor's bin keys and cell order, or a sharkForecast.Forecast (device to device when this planner runs on the
+        forecast's context -- device_context= -- and the forecast is that context's latest; from its host copy otherwise).
+        ValueError for tables that do not match.  None or an empty list clears the tables.  The constructor's own grid stays
+        the table of every call without shark_of."""
+        self._batch_world()  # (the sets lie over the world's bins and cells, and a new world drops them)
+        self._set_prob = put_shark_tables(self._ctx, self._bins, self._cells, grids)
+
+    def _batch_world(self):
+        """astar_batch's world on the context.  Skipped when it is the world this planner set last and nobody has set another
+        since (set_world drops the context's probability sets; the same world again changes no result)."""
+        w = (ac.circles(self.obstacle_list), ac.circles(self.habitat_list), ac.corners(self.boundary_list), self._bins, self._cells,
+             self._prob)
+        stamp = getattr(self._ctx, "_world_stamp", None)
+        if (self._world is not None and stamp is not None and stamp == self._world[0]
+                and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(w, self._world[1]))):
+            return
+        self._ctx.set_world(obstacles=w[0], habitats=w[1], polygon=w[2], bins=w[3], cells=w[4], prob=w[5])
+        self._world = (self._ctx._world_stamp, [np.array(a, dtype=np.float64) for a in w])
 
     def _result(self, r, start):
         if not r["found"]:
@@ -78,9 +110,13 @@ class astar:
         self.visited_nodes = r["visited"].astype(np.float64)
         return self._result(r, self.start)
 
-    def astar_batch(self, starts, limits, weights):
-        self._ctx.set_world(obstacles=ac.circles(self.obstacle_list), habitats=ac.circles(self.habitat_list),
-                            polygon=ac.corners(self.boundary_list), bins=self._bins, cells=self._cells, prob=self._prob)
+    def astar_batch(self, starts, limits, weights, shark_of=None):
+        """len(starts) searches in one launch.  shark_of [E]: instance i is searched against table shark_of[i] of
+        set_shark_grids and equals an astar object built on that table; without it every instance reads the constructor's grid."""
+        sets = None if shark_of is None else shark_set_indices(shark_of, len(starts), self.n_shark_sets)
+        self._batch_world()
+        if sets is not None and self._ctx.n_prob_sets != self.n_shark_sets:
+            self._ctx.set_prob_sets(self._set_prob)  # (another user of the context replaced its sets, or set a world)
         res = ac.run(self._ctx, "astar_fixLenSOG", [tuple(map(float, s)) for s in starts], limits=[float(v) for v in limits],
-                     weights=[float(w) for w in weights], velocity=float(self.velocity), cap_nodes=self.cap_nodes)
+                     weights=[float(w) for w in weights], velocity=float(self.velocity), cap_nodes=self.cap_nodes, set_of=sets)
         return [self._result(r, starts[i]) for i, r in enumerate(res)]

@@ -2,6 +2,14 @@
 // Included at the end of auvplan.hip (same translation unit: uses auvp_handle, fail, HIPCHK, upload; sq_threshold is world_tables.h's).
 #ifndef AUVP_ASTAR_HOST_H
 #define AUVP_ASTAR_HOST_H
+#include "astar_tables.h"
+
+// astar_sets_kernels.hip (a translation unit of its own, so that this unit's astar_kernel<3> forms keep their code): the top-n
+// tables of the probability sets, and the variant-3 search with a table per instance
+extern "C" hipError_t auvpi_astar_topn_sets_launch(const double* prob, double* topn, int rows, int C, hipStream_t stream);
+extern "C" hipError_t auvpi_astar_sets_launch(const auvp::AstarWorldDev* W, const auvp::AstarParamsDev* P, const auvp::AstarBuffers* B, int n_inst,
+                                              const double* sets_prob, const double* sets_topn, const int32_t* set_of, int pair, int grid,
+                                              hipStream_t stream);
 
 static_assert(sizeof(auvp_astar_summary) == sizeof(auvp::AstarSummary), "astar summary layout");
 
@@ -21,6 +29,11 @@ struct AstarState {
   // cellinfo_clean_cap = capacity (bytes) that has been zeroed since the buffer was (re)allocated
   uint32_t epoch = 0;
   size_t cellinfo_clean_cap = 0;
+  // auvp_astar_batch_sets: top-n tables [G][T][C+1] of the handle's probability sets, built on the first batch (or read-back) that
+  // asks for them and kept while sets_version is the handle's; sets_nan[g]: set g holds a nan and has no table; the batch's set_of
+  DevBuf sets_topn, set_of;
+  unsigned sets_version = ~0u;
+  std::vector<char> sets_nan;
 };
 
 AstarState* astar_of(auvp_handle* h) {
@@ -52,14 +65,7 @@ int astar_build_world(auvp_handle* h, AstarState& S) {
     hab[4 * i + 3] = auvp::sq_threshold(h->w_hab[3 * i + 2]);
   }
   for (size_t i = 0; i < rc.size(); i++) rc[i] = round2_py(h->w_cells[i]);
-  std::vector<double> tmp(C);
-  for (int t = 0; t < T; t++) {
-    std::copy(h->w_prob.begin() + (size_t)t * C, h->w_prob.begin() + (size_t)(t + 1) * C, tmp.begin());
-    std::sort(tmp.begin(), tmp.end(), [](double a, double b) { return a > b; });
-    double tot = 0.0;  // total = 0; total += probabilities[index]  (astar_fixLenSOG.py:526-530)
-    topn[(size_t)t * (C + 1)] = 0.0;
-    for (int i = 0; i < C; i++) { tot += tmp[i]; topn[(size_t)t * (C + 1) + i + 1] = tot; }
-  }
+  auvp::astar_topn_rows(h->w_prob.data(), (size_t)T, (size_t)C, topn.data());  // get_top_n_prob's table (astar_tables.h)
   // Polygon(...).centroid: area-weighted (shoelace) centroid -- shapely is absent; DESIGN.md
   double a2 = 0.0, sx = 0.0, sy = 0.0;
   for (int i = 0; i < V; i++) {
@@ -138,12 +144,47 @@ int astar_build_world(auvp_handle* h, AstarState& S) {
   return AUVP_OK;
 }
 
-}  // namespace
+// The top-n tables of the handle's probability sets (h->d_sets_prob [G][T][C], in place): astar_topn_sets_kernel for rows that
+// fit its LDS, astar_topn_rows on a read-back for longer ones.  A set that holds a nan (its record's absmax, written by
+// prob_set_stats_kernel, is a nan) gets no defined table; astar_batch_run refuses the instances that name it.  h->last_ms: the
+// time of the device route's launch (0 on the host route).
+int astar_build_set_tables(auvp_handle* h, AstarState& S) {
+  const int G = h->n_sets, T = h->W.n_bins, C = h->W.n_cells;
+  const size_t rows = (size_t)G * T, n_in = rows * C, n_out = rows * ((size_t)C + 1);
+  S.sets_version = ~0u;
+  std::vector<auvp::RrtProbSetDev> rec((size_t)G);
+  HIPCHK(h, hipMemcpyAsync(rec.data(), h->d_sets_rec.p, rec.size() * sizeof(auvp::RrtProbSetDev), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  S.sets_nan.assign((size_t)G, 0);
+  for (int g = 0; g < G; g++) S.sets_nan[(size_t)g] = rec[(size_t)g].absmax != rec[(size_t)g].absmax ? 1 : 0;
+  HIPCHK(h, S.sets_topn.reserve(n_out * sizeof(double)));
+  h->last_ms = 0.0;
+  if (C <= auvp::ASTAR_TOPN_DEV_MAX_C) {
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, auvpi_astar_topn_sets_launch(h->d_sets_prob.as<double>(), S.sets_topn.as<double>(), (int)rows, C, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    h->last_ms = ms;
+  } else {
+    std::vector<double> prob(n_in), topn(n_out, 0.0);
+    HIPCHK(h, hipMemcpyAsync(prob.data(), h->d_sets_prob.p, n_in * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int g = 0; g < G; g++)  // (std::sort on a row with a nan is not defined: such a set's table stays zero)
+      if (!S.sets_nan[(size_t)g])
+        auvp::astar_topn_rows(prob.data() + (size_t)g * T * C, (size_t)T, (size_t)C, topn.data() + (size_t)g * T * ((size_t)C + 1));
+    HIPCHK(h, hipMemcpyAsync(S.sets_topn.p, topn.data(), n_out * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  S.sets_version = h->sets_version;
+  return AUVP_OK;
+}
 
-extern "C" {
-
-int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const double* goals, const double* limits,
-                     const auvp_astar_params* p, int32_t flags) {
+// auvp_astar_batch (set_of null) and auvp_astar_batch_sets: one host function, so that epochs, visited words, the PAIR choice and
+// the redo are the same text for both
+int astar_batch_run(auvp_handle* h, int32_t E, const double* starts, const double* goals, const double* limits,
+                    const auvp_astar_params* p, int32_t flags, const int32_t* set_of) {
   if (!h) return AUVP_ERR_ARG;
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   if (E <= 0 || !starts || !p || p->variant < 0 || p->variant > 3) return fail(h, AUVP_ERR_ARG, "bad arguments");
@@ -151,11 +192,25 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
   if (p->variant >= 2 && !limits) return fail(h, AUVP_ERR_ARG, "pathLenLimit required for the fixLen variants");
   if (p->variant >= 1 && h->w_poly.size() < 6) return fail(h, AUVP_ERR_ARG, "boundary polygon needs >= 3 vertices");
   if (p->cap_nodes < 16) return fail(h, AUVP_ERR_ARG, "cap_nodes too small");
+  const bool sets = set_of != nullptr;
+  if (sets) {
+    if (p->variant != 3) return fail(h, AUVP_ERR_ARG, "a table per instance is astar_fixLenSOG's (variant 3), not variant %d", p->variant);
+    if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle (auvp_world_set_prob_sets)");
+    for (int e = 0; e < E; e++)
+      if (set_of[e] < 0 || set_of[e] >= h->n_sets) return fail(h, AUVP_ERR_ARG, "instance %d: set %d outside [0, %d)", e, set_of[e], h->n_sets);
+  }
   HIPCHK(h, hipSetDevice(h->device));
   AstarState& S = *astar_of(h);
   S.ready = false;
   int rc;
   if (S.world_version != h->world_version && (rc = astar_build_world(h, S))) return rc;
+  if (sets) {
+    if (S.sets_version != h->sets_version && (rc = astar_build_set_tables(h, S))) return rc;
+    for (int e = 0; e < E; e++)
+      if (S.sets_nan[(size_t)set_of[e]])
+        return fail(h, AUVP_ERR_ARG, "probability set %d holds a nan: it has no top-n table (instance %d)", set_of[e], e);
+    if ((rc = upload(h, S.set_of, set_of, (size_t)E))) return rc;
+  }
   auvp::AstarParamsDev& P = S.P;
   P.variant = p->variant; P.cap_nodes = p->cap_nodes; P.flags = flags;
   if (h->opt_on(OPT_ASTAR_NO_LIST)) P.flags |= AUVP_KFLAG_ASTAR_NO_LIST;
@@ -213,6 +268,15 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
   h->pipe_fallback_last = 0;
   const int grid = (E + auvp::ASTAR_WAVES - 1) / auvp::ASTAR_WAVES;
   bool pair = false;
+  // variant 3, plain or with a table per instance (astar_sets_kernels.hip)
+  auto launch3 = [&](bool two) -> hipError_t {
+    if (sets)
+      return auvpi_astar_sets_launch(&S.W, &P, &B, (int)E, h->d_sets_prob.as<double>(), S.sets_topn.as<double>(), S.set_of.as<int32_t>(), two ? 1 : 0,
+                                     grid, h->stream);
+    if (two) hipLaunchKernelGGL((auvp::astar_kernel<3, true>), dim3(grid), dim3(auvp::ASTAR_WAVES * 128), 0, h->stream, S.W, P, B, (int)E);
+    else hipLaunchKernelGGL(auvp::astar_kernel<3>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E);
+    return hipSuccess;
+  };
   switch (P.variant) {
     case 0: hipLaunchKernelGGL(auvp::astar_kernel<0>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E); break;
     case 1: hipLaunchKernelGGL(auvp::astar_kernel<1>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E); break;
@@ -222,8 +286,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
       // forces the choice.  Not with a visited array the caller carries over (KEEP_VISITED): a batch that had to be repeated on
       // the one-wavefront kernel (pipeline fallback, below) could not get it back.
       pair = S.W.g_ncol > 0 && !(flags & AUVP_FLAG_KEEP_VISITED) && h->opt_flag(OPT_ASTAR_PAIR, E <= (size_t)8 * (size_t)h->n_cu);
-      if (pair) hipLaunchKernelGGL((auvp::astar_kernel<3, true>), dim3(grid), dim3(auvp::ASTAR_WAVES * 128), 0, h->stream, S.W, P, B, (int)E);
-      else hipLaunchKernelGGL(auvp::astar_kernel<3>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E);
+      HIPCHK(h, launch3(pair));
       break;
     }
   }
@@ -250,7 +313,7 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
       S.epoch++;
       P.epoch = S.epoch;
       pair = false;
-      hipLaunchKernelGGL(auvp::astar_kernel<3>, dim3(grid), dim3(auvp::ASTAR_WAVES * 64), 0, h->stream, S.W, P, B, (int)E);
+      HIPCHK(h, launch3(false));  // (with sets: the one-wavefront sets form, every instance on its own table again)
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipEventRecord(h->ev1, h->stream));  // (the time the caller waited: both searches)
       HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -262,6 +325,35 @@ int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const doub
   h->last_grid = grid; h->last_block = auvp::ASTAR_WAVES * (pair ? 128 : 64); h->last_lds = 0;
   S.E = E;
   S.ready = true;
+  return AUVP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int auvp_astar_batch(auvp_handle* h, int32_t E, const double* starts, const double* goals, const double* limits,
+                     const auvp_astar_params* p, int32_t flags) {
+  return astar_batch_run(h, E, starts, goals, limits, p, flags, nullptr);
+}
+
+int auvp_astar_batch_sets(auvp_handle* h, int32_t E, const double* starts, const double* limits, const auvp_astar_params* p, int32_t flags,
+                          const int32_t* set_of) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!set_of) return fail(h, AUVP_ERR_ARG, "set_of required");
+  return astar_batch_run(h, E, starts, nullptr, limits, p, flags, set_of);
+}
+
+int auvp_astar_sets_topn(auvp_handle* h, double* out) {
+  if (!h || !out) return AUVP_ERR_ARG;
+  if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle (auvp_world_set_prob_sets)");
+  HIPCHK(h, hipSetDevice(h->device));
+  AstarState& S = *astar_of(h);
+  int rc;
+  if (S.sets_version != h->sets_version && (rc = astar_build_set_tables(h, S))) return rc;
+  const size_t n = (size_t)h->n_sets * h->W.n_bins * ((size_t)h->W.n_cells + 1);
+  HIPCHK(h, hipMemcpyAsync(out, S.sets_topn.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return AUVP_OK;
 }
 

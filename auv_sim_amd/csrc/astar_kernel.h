@@ -158,9 +158,26 @@ struct AstarPairBox {
   int ts_[8], tb[8], key[8];
 };
 
+#ifdef AUVP_ASTAR_SETS
+// astar_sets_kernels.hip only (it defines AUVP_ASTAR_SETS; auvplan.hip never sees these lines): a table per search instance.
+// Instance e reads prob [T,C] / topn [T,C+1] of set set_of[e] -- the handle's probability sets and the top-n tables
+// astar_topn_sets_kernel made of them -- through a kernel argument of its own; everything else is W's, shared by the batch.
+struct AstarSetsDev {
+  const double* prob;     // [G][T][C]
+  const double* topn;     // [G][T][C+1]
+  const int32_t* set_of;  // [E], every entry in [0, G) (checked on the host)
+};
+#endif
+
 // one instantiation per variant (VARIANT = AstarParamsDev::variant): the other variants' state and branches are gone
+#ifdef AUVP_ASTAR_SETS
+template <int VARIANT, bool PAIR = false>
+__global__ __launch_bounds__(ASTAR_WAVES * 64 * (PAIR ? 2 : 1)) void astar_sets_kernel(AstarWorldDev W, AstarParamsDev P, AstarBuffers B, int n_inst,
+                                                                                       AstarSetsDev SD) {
+#else
 template <int VARIANT, bool PAIR = false>
 __global__ __launch_bounds__(ASTAR_WAVES * 64 * (PAIR ? 2 : 1)) void astar_kernel(AstarWorldDev W, AstarParamsDev P, AstarBuffers B, int n_inst) {
+#endif
   static_assert(!PAIR || VARIANT == 3, "the paired form is variant 3's");
   __shared__ AstarPairBox s_box[PAIR ? ASTAR_WAVES : 1];
   __shared__ int32_t s_hopen[ASTAR_WAVES][ASTAR_MAX_HAB];
@@ -198,6 +215,19 @@ __global__ __launch_bounds__(ASTAR_WAVES * 64 * (PAIR ? 2 : 1)) void astar_kerne
   if (PAIR && threadIdx.x < ASTAR_WAVES) { s_box[threadIdx.x].seq_m = 0; s_box[threadIdx.x].seq_x = 0; s_box[threadIdx.x].stop = 0; }
   __syncthreads();
   if (ep >= n_inst) return;  // no workgroup barrier after this point
+#ifdef AUVP_ASTAR_SETS
+  {
+    // this instance's tables in place of the world's (both wavefronts of a PAIR instance: the second one reads them as well)
+    // (AUVP_ASTAR_SETS_READS, experiment builds only -- profiles/astar_shark_sets.md: bit 0 = prob from the set, bit 1 = topn from
+    // the set, the other one stays the world's; the product is 3)
+#ifndef AUVP_ASTAR_SETS_READS
+#define AUVP_ASTAR_SETS_READS 3
+#endif
+    const size_t sg = (size_t)uni(SD.set_of[ep]);
+    if (AUVP_ASTAR_SETS_READS & 1) W.prob = SD.prob + sg * (size_t)T * (size_t)C;
+    if (AUVP_ASTAR_SETS_READS & 2) W.topn = SD.topn + sg * (size_t)T * ((size_t)C + 1);
+  }
+#endif
   constexpr int V = VARIANT;
   AstarPairBox* box = &s_box[PAIR ? wave : 0];
   (void)box;
@@ -790,6 +820,7 @@ __global__ __launch_bounds__(ASTAR_WAVES * 64 * (PAIR ? 2 : 1)) void astar_kerne
   }
 }
 
+#ifndef AUVP_ASTAR_SETS  // (astar_sets_kernels.hip brings the search kernel alone: the path pass reads no probability table)
 // Backtrack of the popped goal node (:231-243 / :319-333 / :593-618) and, for variant 3, smoothPath
 // (:404-440).  out per instance: path [L,3] root->leaf x,y,round(time_stamp,2); cost_list [L] leaf->root;
 // node_path [L,8] root->leaf; smooth [<=L,3].  One wave per instance.
@@ -872,6 +903,7 @@ __global__ __launch_bounds__(64) void astar_path_kernel(AstarWorldDev W, AstarPa
     if (status) s.status = status;
   }
 }
+#endif
 
 }  // namespace auvp
 #endif

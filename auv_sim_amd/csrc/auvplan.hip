@@ -46,6 +46,10 @@ extern "C" hipError_t auvpi_rrt_leaf_grid_launch(const auvp::WorldDev* W, const 
 extern "C" hipError_t auvpi_prob_set_stats_launch(const double* prob, long long n_per_set, int n_sets, auvp::RrtProbSetDev* sets,
                                                   hipStream_t stream);
 
+#ifdef AUVP_PIPE_DIAG
+extern "C" hipError_t auvpi_astar_sets_diag(const int* cfg8);  // (astar_sets_kernels.hip; the other launchers: astar_host.h)
+#endif
+
 static_assert(sizeof(auvp_rrt_summary) == sizeof(RrtSummary), "summary layout");
 static_assert(sizeof(struct auvp_rrt_group_best) == sizeof(RrtGroupBest), "group record layout");
 
@@ -120,6 +124,7 @@ struct auvp_handle {
   // probability sets (auvp_world_set_prob_sets): n_sets tables [T,C] over the world's bins and cells and their records; grids:
   // the prepared batch has a set per episode (auvp_rrt_set_episode_grids) and its leaf pass is rrt_leaf_grid_kernel
   int n_sets = 0;
+  unsigned sets_version = 0;  // bumped whenever the sets change or go: what is derived from them (astar_host.h: top-n tables) is stale
   bool grids = false;
   DevBuf d_sets_prob, d_sets_rec, d_set_of;
   double last_ms = 0.0;
@@ -290,6 +295,8 @@ int auvp_create(int device, auvp_handle** out) {
     if (const char* e = getenv("AUVP_DIAG_SPIN")) cfg[0] = atoi(e);
     if (const char* e = getenv("AUVP_DIAG_JITTER")) (void)sscanf(e, "%d,%d,%d,%d,%d", &cfg[1], &cfg[2], &cfg[3], &cfg[4], &cfg[5]);
     if (hipMemcpyToSymbol(HIP_SYMBOL(auvp_diag_cfg), cfg, sizeof cfg) != hipSuccess) { auvp_destroy(h); return AUVP_ERR_HIP; }
+    // (a device variable per translation unit: astar_sets_kernels.hip's paired kernel reads its own copy)
+    if (auvpi_astar_sets_diag(cfg) != hipSuccess) { auvp_destroy(h); return AUVP_ERR_HIP; }
   }
 #endif
   *out = h;
@@ -361,6 +368,7 @@ int auvp_world_set(auvp_handle* h, const double* obstacles, int32_t O, const dou
   if (T > RRT_MAX_BINS) return fail(h, AUVP_ERR_ARG, "n_bins %d > %d", T, RRT_MAX_BINS);
   HIPCHK(h, hipSetDevice(h->device));
   h->n_sets = 0;  // the probability sets belonged to the world that goes (its bins and cells)
+  h->sets_version++;
   h->grids = false;
   WorldIn in;
   in.obstacles = obstacles; in.O = O; in.habitats = habitats; in.H = H; in.polygon = polygon; in.V = V;
@@ -828,6 +836,7 @@ int auvp_rrt_run(auvp_handle* h) {
 
 int auvp_world_set_prob_sets(auvp_handle* h, int32_t n_sets, const double* prob_host, const void* prob_dev) {
   if (!h) return AUVP_ERR_ARG;
+  h->sets_version++;
   if (n_sets == 0 && !prob_host && !prob_dev) {
     h->n_sets = 0;
     h->grids = false;

@@ -59,6 +59,47 @@ def pack_shark_grid(sharkGrid):
     return bins, cells, prob.reshape(len(keys), len(cell_keys))
 
 
+def put_shark_tables(ctx, own_bins, own_cells, grids):
+    """set_shark_grids of RRT and astar_fixLenSOG.astar: the tables of `grids` onto ctx's probability sets (Context.set_prob_sets),
+    checked against the planner's own bins [T,2] and cells [C,4].  `grids`: a list of sharkGrid dicts with the planner's bin keys
+    and cell order, or a sharkForecast.Forecast -- its prob [F, R+1, C] goes device to device while it is still its context's
+    latest forecast on ctx's device, from its host copy otherwise; None or an empty list clears the sets.  ValueError for
+    tables that do not match.  Returns the host copy [G, T, C], None when cleared."""
+    if grids is None or (isinstance(grids, (list, tuple)) and len(grids) == 0):
+        ctx.set_prob_sets()
+        return None
+    T, Cn = len(own_bins), len(own_cells)
+    if hasattr(grids, "prob") and hasattr(grids, "cell_bounds"):  # a Forecast
+        fc = grids
+        if fc.prob.ndim != 3 or fc.prob.shape[1] != T:
+            raise ValueError("the forecast has %d time bins (rounds + 1), the planner %d" % (fc.prob.shape[1], T))
+        cb = np.array(fc.cell_bounds, dtype=np.float64).reshape(-1, 4)
+        if cb.shape != own_cells.shape or not np.array_equal(cb, own_cells):
+            raise ValueError("the forecast's cell list is not the planner's")
+        src = getattr(fc, "ctx", None)
+        if src is not None and src.device == ctx.device and getattr(src, "sf_serial", None) == getattr(fc, "serial", -1):
+            ptr, F, Tf, Cf = src.sf_prob_dev()
+            if (F, Tf, Cf) != fc.prob.shape:
+                raise ValueError("the forecast's device copy is [%d, %d, %d], not %r" % (F, Tf, Cf, fc.prob.shape))
+            ctx.set_prob_sets(n_sets=F, prob_dev=ptr)
+        else:  # (a forecast of another device, or one its context has since replaced: from the host copy)
+            ctx.set_prob_sets(fc.prob)
+        return np.array(fc.prob, dtype=np.float64)
+    tabs = []
+    for g, grid in enumerate(grids):
+        bins, cells, prob = pack_shark_grid(grid)
+        if bins.shape != own_bins.shape or not np.array_equal(bins, own_bins):
+            raise ValueError("shark grid %d: its time bins are not the constructor's" % g)
+        if cells.shape != own_cells.shape or not np.array_equal(cells, own_cells):
+            raise ValueError("shark grid %d: its cells are not the constructor's, in the constructor's order" % g)
+        tabs.append(prob)
+    if T == 0 or Cn == 0:
+        raise ValueError("shark tables need a planner whose own grid has time bins and cells")
+    host = np.stack(tabs)
+    ctx.set_prob_sets(host)
+    return host
+
+
 def habitat_keep_bits(masks, n_habitats, n_episodes):
     """exploring_batch's habitat_masks -> [E] ints (bit h: habitats[h] is on the episode's list): None (all of them), [E] ints,
     or [E, H] booleans"""
@@ -172,40 +213,7 @@ class RRT:
         the planner's without leaving HBM (R + 1 must be the planner's bin count and the cell list the planner's).  ValueError
         otherwise.  None or an empty list clears the tables.  The constructor's own grid stays the table of every call
         without shark_of."""
-        if grids is None or (isinstance(grids, (list, tuple)) and len(grids) == 0):
-            self._ctx.set_prob_sets()
-            self._set_prob = None
-            return
-        T, Cn = len(self._bins), len(self._cells)
-        if hasattr(grids, "prob") and hasattr(grids, "cell_bounds"):  # a Forecast
-            fc = grids
-            if fc.prob.ndim != 3 or fc.prob.shape[1] != T:
-                raise ValueError("the forecast has %d time bins (rounds + 1), the planner %d" % (fc.prob.shape[1], T))
-            cb = np.array(fc.cell_bounds, dtype=np.float64).reshape(-1, 4)
-            if cb.shape != self._cells.shape or not np.array_equal(cb, self._cells):
-                raise ValueError("the forecast's cell list is not the planner's")
-            src = getattr(fc, "ctx", None)
-            if src is not None and src.device == self._ctx.device and getattr(src, "sf_serial", None) == getattr(fc, "serial", -1):
-                ptr, F, Tf, Cf = src.sf_prob_dev()
-                if (F, Tf, Cf) != fc.prob.shape:
-                    raise ValueError("the forecast's device copy is [%d, %d, %d], not %r" % (F, Tf, Cf, fc.prob.shape))
-                self._ctx.set_prob_sets(n_sets=F, prob_dev=ptr)
-            else:  # (a forecast of another device, or one its context has since replaced: from the host copy)
-                self._ctx.set_prob_sets(fc.prob)
-            self._set_prob = np.array(fc.prob, dtype=np.float64)
-            return
-        tabs = []
-        for g, grid in enumerate(grids):
-            bins, cells, prob = pack_shark_grid(grid)
-            if bins.shape != self._bins.shape or not np.array_equal(bins, self._bins):
-                raise ValueError("shark grid %d: its time bins are not the constructor's" % g)
-            if cells.shape != self._cells.shape or not np.array_equal(cells, self._cells):
-                raise ValueError("shark grid %d: its cells are not the constructor's, in the constructor's order" % g)
-            tabs.append(prob)
-        if T == 0 or Cn == 0:
-            raise ValueError("shark tables need a planner whose own grid has time bins and cells")
-        self._set_prob = np.stack(tabs)
-        self._ctx.set_prob_sets(self._set_prob)
+        self._set_prob = put_shark_tables(self._ctx, self._bins, self._cells, grids)
 
     # ------------------------------------------------------------------ reference API
     def exploring(self, initial, habitats, plot_interval, bin_interval, v, shark_interval, traj_time_stamp=False,

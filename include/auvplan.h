@@ -359,6 +359,18 @@ int auvp_astar_hab_left(auvp_handle* h, int32_t instance, int32_t* out);
  * AUVP_FLAG_KEEP_VISITED ([E][vx*600] bytes, row-major [x_pos][y_pos]) and read it back afterwards */
 int auvp_astar_set_visited(auvp_handle* h, int32_t n_instances, int32_t variant, const uint8_t* bitmap);
 int auvp_astar_get_visited(auvp_handle* h, int32_t instance, uint8_t* bitmap);
+/* A shark-occupancy table per search instance (astar_fixLenSOG, variant 3 only): auvp_astar_batch with instance e reading the
+ * probabilities and the top-n heuristic table of probability set set_of[e] (auvp_world_set_prob_sets) in place of the world's.
+ * The top-n tables of the sets are built on the device on the first call that needs them and kept until auvp_world_set or
+ * auvp_world_set_prob_sets replaces what they were built from.  Flags, visited arrays, expansion log and every read-back call
+ * are auvp_astar_batch's.  AUVP_ERR_STATE: no sets on the handle; AUVP_ERR_ARG: set_of[e] outside [0, n_sets) (the message
+ * names e), params->variant != 3, or an instance names a set that holds a nan (the message names the set: a nan has no place
+ * in the table's descending order).  A call that fails launches no search. */
+int auvp_astar_batch_sets(auvp_handle* h, int32_t n_instances, const double* starts, const double* limits,
+                          const auvp_astar_params* params, int32_t flags, const int32_t* set_of /* [E] */);
+/* The sets' top-n tables as the searches read them: out [n_sets, T, C+1], out[g][t][0] = 0, out[g][t][i+1] = out[g][t][i] + the
+ * i-th largest of prob[g][t] (get_top_n_prob, astar_fixLenSOG.py:516-531).  The rows of a set that holds a nan are unspecified. */
+int auvp_astar_sets_topn(auvp_handle* h, double* out);
 
 /* ---- shark occupancy / AUV detection grids ------------------------------------------------------
  * SharkOccupancyGrid.convert (path_planning/sharkOccupancyGrid.py:47-74): the producer of the
