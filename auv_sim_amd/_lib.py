@@ -137,6 +137,8 @@ def load():
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     L.auvp_math_dev.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
+    if hasattr(L, "auvp_theta_chain_dev"):  # (as above: an earlier build loaded for a comparison has no such probe)
+        L.auvp_theta_chain_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     L.auvp_nn_closest_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _ip, _ip]
     L.auvp_random_stream_dev.argtypes = [vp, C.c_uint64, C.c_int32, _dp]
     L.auvp_rrt_phase_clocks.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -621,6 +623,15 @@ class Context:
         o0, o1 = np.zeros_like(a), np.zeros_like(a)
         self._chk(self.L.auvp_math_dev(self.h, self.MATH_OPS[op], len(a), _p(a), _p(b), _p(o0), _p(o1)))
         return (o0, o1) if op == "sincos" else o0
+
+    def theta_chain(self, theta0, phi):
+        """auvp_theta_chain_dev: rows_theta_chain_dpp on its own.  theta0 [W, 4] (one per 16-lane row), phi [W, 64] (one per lane)
+        -> [W, 64], lane rl of a row: (((theta0 + phi_0) + phi_1) + ... + phi_rl) of its row (lane 15: lane 14's sum)"""
+        theta0, phi = _f64(theta0, (-1, 4)), _f64(phi, (-1, 64))
+        assert len(theta0) == len(phi)
+        out = np.zeros_like(phi)
+        self._chk(self.L.auvp_theta_chain_dev(self.h, len(phi), _p(theta0), _p(phi), _p(out)))
+        return out
 
     def random_stream(self, seed, n):
         out = np.zeros(n)

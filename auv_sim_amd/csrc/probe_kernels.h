@@ -135,6 +135,16 @@ __global__ void math_probe_kernel(int op, int n, const double* __restrict__ a, c
   o1[i] = r1;
 }
 
+// rows_theta_chain_dpp (rrt_rows_kernel.h) on its own: one wavefront per 64 phis, a start angle per 16-lane row.  Every lane takes
+// part (the helper expects the whole wavefront): the grid is exactly n_waves workgroups of one wavefront
+__global__ __launch_bounds__(64) void theta_chain_probe_kernel(const double* __restrict__ theta0, const double* __restrict__ phi,
+                                                               double* __restrict__ out) {
+  const int lane = lane_id();
+  const size_t w = blockIdx.x;
+  const double t0 = theta0[w * 4 + (size_t)(lane >> 4)], p = phi[w * 64 + (size_t)lane];
+  out[w * 64 + (size_t)lane] = rows_theta_chain_dpp(t0, p);
+}
+
 __global__ __launch_bounds__(64) void random_probe_kernel(const uint32_t* __restrict__ mt, int n, double* __restrict__ out) {
   __shared__ uint32_t s[624];
   const int lane = lane_id();
@@ -310,6 +320,22 @@ int auvp_math_dev(auvp_handle* h, int32_t op, int32_t n, const double* a, const 
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(out0, o, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(out1, o + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return AUVP_OK;
+}
+
+int auvp_theta_chain_dev(auvp_handle* h, int32_t n_waves, const double* theta0, const double* phi, double* out) {
+  if (!h || n_waves < 0 || !theta0 || !phi || !out) return AUVP_ERR_ARG;
+  if (n_waves == 0) return AUVP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload(h, h->d_tmp0, theta0, (size_t)n_waves * 4))) return rc;
+  if ((rc = upload(h, h->d_tmp1, phi, (size_t)n_waves * 64))) return rc;
+  HIPCHK(h, h->d_tmp2.reserve((size_t)n_waves * 64 * sizeof(double)));
+  hipLaunchKernelGGL(theta_chain_probe_kernel, dim3(n_waves), dim3(64), 0, h->stream, h->d_tmp0.as<double>(), h->d_tmp1.as<double>(),
+                     h->d_tmp2.as<double>());
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(out, h->d_tmp2.p, (size_t)n_waves * 64 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return AUVP_OK;
 }

@@ -312,10 +312,8 @@
       wave_sync();
 #endif
       // theta += phi, left to right: lane s ends with (((theta0 + phi_0) + phi_1) + ... + phi_s); untaken and idle lanes add
-      // an exact 0.0 (rows_theta_chain: the phis go through the row's LDS scratch)
-      inc[rl] = phi;
-      wave_sync();
-      const double th = rows_theta_chain(cth, inc);
+      // an exact 0.0 (rows_theta_chain_dpp: the phis cross the row's lanes as 64-bit DPP broadcasts, no LDS)
+      const double th = rows_theta_chain_dpp(cth, phi);
       const double myth = (rl == 15) ? cth : th;  // lane 15: the pass-entry angle
       double sn, cs;
       auvp_sincos_sk(myth, &sn, &cs);

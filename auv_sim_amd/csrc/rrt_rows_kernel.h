@@ -6,7 +6,7 @@
 // vector instruction serves four episodes: what was wave-uniform (and lived in scalar registers) becomes row-uniform
 // (the same value in the 16 lanes of a row), ballots are cut into 16-bit row masks, cross-lane reads stay inside a
 // row.  A steer of up to 30 sub-arcs takes two passes of 15 (lane 15 of a row carries the pass-entry angle), the
-// running sums keep the reference's left-to-right order (theta by a DPP row shift chain, x/y/t/length by four lanes
+// running sums keep the reference's left-to-right order (theta by a chain of 64-bit DPP row broadcasts, x/y/t/length by four lanes
 // per row through LDS).  The results are bit-identical to rrt_explore_kernel's; rrt_leaf_kernel finishes both.
 //
 // LDS per episode: the MT19937 state (2 496 B), one scratch block (the tempered random() window of a pass, then the
@@ -85,84 +85,52 @@ __device__ __forceinline__ double row_prev_f64(double v, double first) {
 }
 
 // theta += phi, left to right, for the four rows of a wavefront at once: every lane ends with
-// (((theta0 + phi_0) + phi_1) + ... + phi_rl), phi_j = the value lane j of its row wrote to `row_phi[j]`.  Lane s adds
-// phi_0 .. phi_s itself, the values broadcast out of LDS, under an exec mask that drops lanes rl < j at step j: ONE vector
-// instruction per step (the DPP row-shift chain this replaces cost five: two v_mov_dpp + the add + the merge of the first
-// lane).  The masks are constants -- lanes with (lane & 15) >= j -- and only shrink, so the LDS reads issued under them still
-// reach every lane that will use them; four reads stay in flight.  Expects all 64 lanes enabled at the call (the kernels
-// call it from wave-uniform control flow only: the step masks are absolute) and restores the mask it found.
-__device__ __forceinline__ double rows_theta_chain(double theta0, const double* row_phi) {
-  double th = theta0, t0, t1, t2, t3;
-  const uint32_t a = (uint32_t)(size_t)((const __attribute__((address_space(3))) double*)row_phi);
-  // (the entry mask is saved and put back: should the compiler ever lower an enclosing condition as divergent, lanes that were
-  // masked off stay off -- ADVICE r5; one scalar move)
+// (((theta0 + phi_0) + phi_1) + ... + phi_rl), phi_j = the `phi` of lane j of its row.  Lane s adds phi_0 .. phi_s itself, under
+// an exec mask that drops lanes rl < j at step j: ONE vector instruction per step, and no LDS -- step j reads lane j of every row
+// through the 64-bit DPP row broadcast (row_newbcast:j).  (Before, the phis went through the row's LDS scratch: a ds_write_b64, a
+// wave barrier and fifteen ds_read_b64 broadcasts per pass, each with its wait on the chain -- 1 340 cycles per wave and trip,
+// profiles/rows_theta_dpp.md; before that, a DPP row-shift chain of five instructions per step.)
+// 64-bit DPP exists for VOP1 / VOP2 encodings only and v_add_f64 is VOP3 (the assembler: "dpp variant of this instruction is
+// not supported"), so a step is v_fmac_f64_dpp with a register pair that holds 1.0: th = fma(phi_j, 1.0, th).  The product by
+// 1.0 is exact for every input, the fma then rounds th + phi_j once -- v_add_f64's result bit for bit, signed zeros and
+// infinities included (tests/test_gpu_theta_chain.py holds the device to it).  The masks are constants -- lanes with
+// (lane & 15) >= j -- so lane j itself is on when its phi is fetched and a lane's own sum stops at phi_rl.  (Fifteen steps,
+// j = 0 .. 14: lane 15, the kernels' pass-entry lane, ends with lane 14's sum and its own phi is never read.)  Expects all 64
+// lanes enabled at the call (the kernels call it from wave-uniform control flow only: the step masks are absolute) and restores
+// the mask it found (should the compiler ever lower an enclosing condition as divergent, lanes that were masked off stay off).
+// Wait states (nothing inside an asm statement is padded; LLVM's gfx940 hazard recognizer): a DPP instruction needs 2 after a
+// VALU write of ANY vector register it reads -- `phi` comes out of the division's last v_fmac right before the call, hence the
+// opening s_mov_b64 + s_nop 0; between steps `th` is written by one fmac and read by the next, and the two scalar exec moves
+// are those two states.  (A VALU write of EXEC would need 5; these writes are scalar and not in that rule.)
+__device__ __forceinline__ double rows_theta_chain_dpp(double theta0, double phi) {
+  double th = theta0;
+  const double one = 1.0;
   unsigned long long exec_in;
+#define AUVP_THETA_STEP(J) "v_fmac_f64_dpp %[th], %[phi], %[one] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define AUVP_THETA_MASK(M) "s_mov_b32 exec_lo, " #M "\n\ts_mov_b32 exec_hi, " #M "\n\t"
   __asm__ volatile(
       "s_mov_b64 %[sv], exec\n\t"
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "ds_read_b64 %[t0], %[a] offset:0\n\t"
-      "ds_read_b64 %[t1], %[a] offset:8\n\t"
-      "ds_read_b64 %[t2], %[a] offset:16\n\t"
-      "ds_read_b64 %[t3], %[a] offset:24\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "v_add_f64 %[th], %[th], %[t0]\n\t"
-      "ds_read_b64 %[t0], %[a] offset:32\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfffefffe\n\ts_mov_b32 exec_hi, 0xfffefffe\n\t"
-      "v_add_f64 %[th], %[th], %[t1]\n\t"
-      "ds_read_b64 %[t1], %[a] offset:40\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfffcfffc\n\ts_mov_b32 exec_hi, 0xfffcfffc\n\t"
-      "v_add_f64 %[th], %[th], %[t2]\n\t"
-      "ds_read_b64 %[t2], %[a] offset:48\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfff8fff8\n\ts_mov_b32 exec_hi, 0xfff8fff8\n\t"
-      "v_add_f64 %[th], %[th], %[t3]\n\t"
-      "ds_read_b64 %[t3], %[a] offset:56\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfff0fff0\n\ts_mov_b32 exec_hi, 0xfff0fff0\n\t"
-      "v_add_f64 %[th], %[th], %[t0]\n\t"
-      "ds_read_b64 %[t0], %[a] offset:64\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xffe0ffe0\n\ts_mov_b32 exec_hi, 0xffe0ffe0\n\t"
-      "v_add_f64 %[th], %[th], %[t1]\n\t"
-      "ds_read_b64 %[t1], %[a] offset:72\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xffc0ffc0\n\ts_mov_b32 exec_hi, 0xffc0ffc0\n\t"
-      "v_add_f64 %[th], %[th], %[t2]\n\t"
-      "ds_read_b64 %[t2], %[a] offset:80\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xff80ff80\n\ts_mov_b32 exec_hi, 0xff80ff80\n\t"
-      "v_add_f64 %[th], %[th], %[t3]\n\t"
-      "ds_read_b64 %[t3], %[a] offset:88\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xff00ff00\n\ts_mov_b32 exec_hi, 0xff00ff00\n\t"
-      "v_add_f64 %[th], %[th], %[t0]\n\t"
-      "ds_read_b64 %[t0], %[a] offset:96\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfe00fe00\n\ts_mov_b32 exec_hi, 0xfe00fe00\n\t"
-      "v_add_f64 %[th], %[th], %[t1]\n\t"
-      "ds_read_b64 %[t1], %[a] offset:104\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xfc00fc00\n\ts_mov_b32 exec_hi, 0xfc00fc00\n\t"
-      "v_add_f64 %[th], %[th], %[t2]\n\t"
-      "ds_read_b64 %[t2], %[a] offset:112\n\t"
-      "s_waitcnt lgkmcnt(3)\n\t"
-      "s_mov_b32 exec_lo, 0xf800f800\n\ts_mov_b32 exec_hi, 0xf800f800\n\t"
-      "v_add_f64 %[th], %[th], %[t3]\n\t"
-      "s_waitcnt lgkmcnt(2)\n\t"
-      "s_mov_b32 exec_lo, 0xf000f000\n\ts_mov_b32 exec_hi, 0xf000f000\n\t"
-      "v_add_f64 %[th], %[th], %[t0]\n\t"
-      "s_waitcnt lgkmcnt(1)\n\t"
-      "s_mov_b32 exec_lo, 0xe000e000\n\ts_mov_b32 exec_hi, 0xe000e000\n\t"
-      "v_add_f64 %[th], %[th], %[t1]\n\t"
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b32 exec_lo, 0xc000c000\n\ts_mov_b32 exec_hi, 0xc000c000\n\t"
-      "v_add_f64 %[th], %[th], %[t2]\n\t"
+      "s_nop 0\n\t"
+      AUVP_THETA_STEP(0)
+      AUVP_THETA_MASK(0xfffefffe) AUVP_THETA_STEP(1)
+      AUVP_THETA_MASK(0xfffcfffc) AUVP_THETA_STEP(2)
+      AUVP_THETA_MASK(0xfff8fff8) AUVP_THETA_STEP(3)
+      AUVP_THETA_MASK(0xfff0fff0) AUVP_THETA_STEP(4)
+      AUVP_THETA_MASK(0xffe0ffe0) AUVP_THETA_STEP(5)
+      AUVP_THETA_MASK(0xffc0ffc0) AUVP_THETA_STEP(6)
+      AUVP_THETA_MASK(0xff80ff80) AUVP_THETA_STEP(7)
+      AUVP_THETA_MASK(0xff00ff00) AUVP_THETA_STEP(8)
+      AUVP_THETA_MASK(0xfe00fe00) AUVP_THETA_STEP(9)
+      AUVP_THETA_MASK(0xfc00fc00) AUVP_THETA_STEP(10)
+      AUVP_THETA_MASK(0xf800f800) AUVP_THETA_STEP(11)
+      AUVP_THETA_MASK(0xf000f000) AUVP_THETA_STEP(12)
+      AUVP_THETA_MASK(0xe000e000) AUVP_THETA_STEP(13)
+      AUVP_THETA_MASK(0xc000c000) AUVP_THETA_STEP(14)
       "s_mov_b64 exec, %[sv]"
-      : [th] "+v"(th), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [sv] "=&s"(exec_in)
-      : [a] "v"(a)
-      : "memory");
+      : [th] "+v"(th), [sv] "=&s"(exec_in)
+      : [phi] "v"(phi), [one] "v"(one));
+#undef AUVP_THETA_STEP
+#undef AUVP_THETA_MASK
   return th;
 }
 

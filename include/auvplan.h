@@ -495,6 +495,11 @@ int auvp_sincos_dev(auvp_handle* h, int32_t n, const double* x, double* s, doubl
  * 2 math.e ** a (particleFilter.py:103-116); 3 the steer's short division a / b and 4 its square root (rrt_dubins.py:268-281;
  * operands of unexceptional magnitude: auvp_div_plain / auvp_sqrt_plain); 5 hypot(a, b); 6 a / b and 7 sqrt(a) as compiled. */
 int auvp_math_dev(auvp_handle* h, int32_t op, int32_t n, const double* a, const double* b, double* out0, double* out1);
+/* the four-episode RRT kernels' ordered theta sum (rows_theta_chain_dpp, auv_sim_amd/csrc/rrt_rows_kernel.h) on its own, n_waves
+ * wavefronts of four 16-lane rows: theta0 [n_waves * 4] one start angle per row, phi [n_waves * 64] one addend per lane; out
+ * [n_waves * 64], lane rl of a row gets (((theta0 + phi_0) + phi_1) + ... + phi_rl) of its row; fifteen steps, so lane 15 gets lane 14's sum (bit-exactness probe: the sums of
+ * theta += phi in path_planning/rrt_dubins.py:268-281, left to right) */
+int auvp_theta_chain_dev(auvp_handle* h, int32_t n_waves, const double* theta0, const double* phi, double* out);
 /* CPython random() stream of `seed` generated by the wave-level device MT19937 */
 int auvp_random_stream_dev(auvp_handle* h, uint64_t seed, int32_t n, double* out);
 

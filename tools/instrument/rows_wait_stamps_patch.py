@@ -15,7 +15,7 @@ Classes (profiles/rows_trip_lgkm.md):
   3  the candidate loop of the cull (both instances): a REGION, the exact tests' arithmetic included
   4  the accepting path, from `if (acc_)` to the trip's last wave_sync: a REGION (the wait before the bin append lies in it;
      it belongs to a register the compiler reuses, not to a value the source can name, so it cannot be stamped alone)
-  5  a steer pass's theta chain, from the phis' LDS write to the chain's result: a REGION (16 dependent adds included)
+  5  a steer pass's theta chain, from its call to the chain's result: a REGION (the 15 dependent DPP fmacs included)
   6  a steer pass's four chains, from the increments' LDS write to the prefix values read back: a REGION
   7  the stream_ensure calls of a trip (votes and slow path): a REGION
 A pure wait is `stamp; empty asm that reads the value; stamp`: the compiler puts the value's s_waitcnt between the stamps (check
@@ -59,12 +59,12 @@ before("  for (int it = 0; it < P.max_iter; it++) {\n    if (!wave_any(live)) br
        "#define ROWS_WS_OUT(c) do { if (AUVP_ROWS_WAIT_STAMPS == (c)) ws_acc += __builtin_amdgcn_s_memtime() - ws_t0; } while (0)\n#endif\n")
 # 1: the parent's id, where the record is requested
 before("    double cx = 0.0, cy = 0.0, cth = 0.0, ctt = 0.0, clen = 0.0;\n    if (live) {", pure(1, 'asm volatile("" : : "v"(par))'))
-# 2: the record at its first use (pass 0: the phis' write is the last thing before the theta chain needs cth)
-before("      inc[rl] = phi;\n      wave_sync();\n      const double th = rows_theta_chain(cth, inc);",
+# 2: the record at its first use (pass 0: the theta chain is the first thing that needs cth)
+before("      const double th = rows_theta_chain_dpp(cth, phi);",
        "\n#ifdef AUVP_ROWS_WAIT_STAMPS\n      if (AUVP_ROWS_WAIT_STAMPS == 2 && pass == 0) { __builtin_amdgcn_sched_barrier(0); ROWS_WS_IN(2); "
        '__builtin_amdgcn_sched_barrier(0); asm volatile("" : : "v"(cx), "v"(cy), "v"(cth), "v"(ctt), "v"(clen)); ROWS_WS_OUT(2); }\n#endif\n' + IN % 5)
 # 5: the theta chain
-after("      const double th = rows_theta_chain(cth, inc);",
+after("      const double th = rows_theta_chain_dpp(cth, phi);",
       '\n#ifdef AUVP_ROWS_WAIT_STAMPS\n      double th_ws = th;\n      if (AUVP_ROWS_WAIT_STAMPS == 5) { asm volatile("" : "+v"(th_ws)); ROWS_WS_OUT(5); }\n#endif\n')
 # 6: the four chains
 before("      if (rl < 15) { inc[rl] = dx; inc[18 + rl] = dy; inc[36 + rl] = dt; inc[54 + rl] = mv; }", IN % 6)
