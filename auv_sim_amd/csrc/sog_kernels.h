@@ -59,8 +59,10 @@ __global__ __launch_bounds__(256) void sog_count_kernel(SogDev D) {
   }
   if (D.n_cells == 0) return;
   double fb = auvp_floor((x - D.xb_x0) * D.xb_inv_w), fy = auvp_floor((y - D.xb_y0) * D.xb_inv_h);
-  const int bx = fb < 0.0 ? 0 : (fb >= (double)D.n_xbuckets ? D.n_xbuckets - 1 : (int)fb);
-  const int by = fy < 0.0 ? 0 : (fy >= (double)D.n_ybuckets ? D.n_ybuckets - 1 : (int)fy);
+  // (!(f >= 0) and not f < 0: a NaN coordinate goes to bucket 0 without a conversion to int -- it lies in no cell, every
+  // comparison of the containment test below is false, but it has counted in npts above, as in the reference)
+  const int bx = !(fb >= 0.0) ? 0 : (fb >= (double)D.n_xbuckets ? D.n_xbuckets - 1 : (int)fb);
+  const int by = !(fy >= 0.0) ? 0 : (fy >= (double)D.n_ybuckets ? D.n_ybuckets - 1 : (int)fy);
   const int bk = by * D.n_xbuckets + bx;
   const int e = D.xb_off[bk + 1];
   for (int i = D.xb_off[bk]; i < e; i++) {
@@ -437,8 +439,9 @@ extern "C" int auvp_sog_convert(auvp_handle* h, const double* cells, int32_t C, 
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   if (n_pts) hipLaunchKernelGGL(auvp::sog_count_kernel, dim3((n_pts + 255) / 256), dim3(256), 0, h->stream, D);
   hipLaunchKernelGGL(auvp::sog_occ_kernel, dim3((unsigned)((tsg + 255) / 256)), dim3(256), 0, h->stream, D);
-  // the LDS-tiled sums where a tile with its halo fits (count <= 24: 150 KB), with the radius as a compile-time constant up to
-  // eight cells; option SOG_TILE = 0 forces the per-cell sweep of L2, 2 the tiled kernel with the radius at run time
+  // the LDS-tiled sums where the two buffers of a tile with its halo fit 150 KiB (count <= 25: 152 064 B = 148.5 KiB of the CU's
+  // 160; count = 26 would take 156 672 B), with the radius as a compile-time constant up to eight cells; option SOG_TILE = 0
+  // forces the per-cell sweep of L2, 2 the tiled kernel with the radius at run time
   const int tmode = (int)h->opt_num(OPT_SOG_TILE, 1);
   const size_t tile_lds = auvp::sog_tile_bytes(D.count);
   const bool tiled = D.count > 0 && tile_lds <= (size_t)150 * 1024 && tmode != 0;

@@ -37,7 +37,8 @@ def convert(cells, box, cell_size, bin_interval, detect_range, traj_len, pts, ki
     i.cell_size, i.bin_interval, i.detect_range = float(cell_size), float(bin_interval), float(detect_range)
     i.cells, i.traj_len, i.pts = orc._ptr(cells), orc._ptr(tl, _ip), orc._ptr(pts)
     rows, cols = grid_shape(box, cell_size)
-    cap = int(pts[:, 2].max() / bin_interval) + 2 if len(pts) else 1
+    tmax = np.nanmax(pts[:, 2]) if len(pts) and not np.isnan(pts[:, 2]).all() else 0.0  # (a NaN time stamp is in no bin)
+    cap = max(int(tmax / bin_interval), 0) + 2
     bins, grids = np.zeros((cap, 2)), np.zeros((cap, rows, cols))
     occ, auv = np.zeros((rows, cols)), np.zeros((rows, cols))
     o = SogOut()
