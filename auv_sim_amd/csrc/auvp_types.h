@@ -69,12 +69,15 @@ struct WorldDev {
   int32_t hg_n, _pad_hg;
   double hg_x0, hg_y0, hg_inv_w, hg_inv_h;
   const unsigned long long* hg_mask;  // [hg_n * hg_n]
-  // the obstacles once more, reordered along a space-filling curve and cut into 16 slots of 16 (rrt_rows_kernel; built
-  // for <= 256 obstacles).  The collision decision is an OR over (point, obstacle) pairs of d2 <= T_i, so the order in
-  // which a kernel looks at them is free once T_i (which encodes the reference's list order) is fixed.
-  //   os_x, os_y, os_t [256]  centre and threshold, padded with entries that never collide
+  // the obstacles once more, grouped into 16 slots of at most 16 by four median splits of their centres, each along the
+  // group's longer axis (world_tables.h: build_obstacle_slots; the runs of 16 along the Z curve where those cost less)
+  // (rrt_rows_kernel; built for <= 256 obstacles).  The collision decision is an OR over (point, obstacle) pairs of
+  // d2 <= T_i, so the order in which a kernel looks at them is free once T_i (which encodes the reference's list order) is fixed.
+  //   os_x, os_y, os_t [256]  centre and threshold; slot s = entries 16 s .. 16 s + 15, its group first, then padding
+  //                           (entries that never collide), so padding lies inside the slots, not only behind the last
   //   os_r [256]              cull radius >= sqrt(T) as float, -inf for padding
-  //   os_box [16][4]          per slot: x0, y0, x1, y1 of the union of its obstacles' cull squares (empty slot: inverted)
+  //   os_box [16][4]          per slot: x0, y0, x1, y1 of the union of its obstacles' cull squares (empty slot: inverted;
+  //                           a slot with a NaN centre: -inf .. inf, never culled)
   const double* os_x;
   const double* os_y;
   const double* os_t;

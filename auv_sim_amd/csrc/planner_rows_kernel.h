@@ -10,7 +10,7 @@
 //   steer (:251-289)       lane s = sub-arc s (two draws each, no data-dependent offsets); theta with its angle_wrap and
 //                          x / y / t are left-to-right DPP row-shift chains (lane s is final after s + 1 steps): no LDS
 //                          scratch at all -- the only LDS an episode owns is its MT19937 state
-//   collision (:435-458)   the obstacles cut into 16 slots of 16 along a space-filling curve (WorldDev::os_*): lane rl
+//   collision (:435-458)   the obstacles grouped into 16 slots of at most 16 by median splits (WorldDev::os_*): lane rl
 //                          keeps slot rl's bounding box, hit slots get the per-obstacle cull against the tight box of the
 //                          path points, survivors the exact d2 <= T_i test (lane = path point, lane 15 = the parent's end)
 //   goal arc (:374-423)    16 samples per row and pass, same cull, early exit at the first pass that is not free

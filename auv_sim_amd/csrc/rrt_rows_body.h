@@ -43,7 +43,7 @@
   double* olx = reinterpret_cast<double*>(smem + plan.tables + (size_t)wg_waves * RW_ROWS * plan.per_ep);
   double* oly = olx + RW_MAX_OBST;
   float* olr = reinterpret_cast<float*>(oly + RW_MAX_OBST);
-  // the spatially sorted tile (WorldDev::os_*): slot s = obstacles 16 s .. 16 s + 15
+  // the tile grouped by median splits (WorldDev::os_*): slot s = entries 16 s .. 16 s + 15, a group of at most 16 + padding
   for (int i = threadIdx.x; i < RW_MAX_OBST; i += blockDim.x) { olx[i] = W.os_x[i]; oly[i] = W.os_y[i]; olr[i] = W.os_r[i]; }
   __syncthreads();
 

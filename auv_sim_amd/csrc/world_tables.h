@@ -259,7 +259,11 @@ inline void build_separable_grid(const double* cells, int C, bool grid_index, Wo
   t.sg_inv_dy = (sg_nrow > 1 && sgy1[sg_nrow - 1] > sgy1[0]) ? (double)(sg_nrow - 1) / (sgy1[sg_nrow - 1] - sgy1[0]) : 0.0;
 }
 
-// spatially sorted obstacle tile + slot boxes for rrt_rows_kernel (auvp_types.h), and obst_area.  Reads ox, oy, ot of `t`
+// obstacle tile in 16 slots of at most 16 + slot boxes for rrt_rows_kernel (auvp_types.h), and obst_area.  Reads ox, oy, ot of `t`.
+// A steer looks into every slot whose box meets its reach square, so the grouping is the one whose boxes are met least often:
+// a four-level median split (every group cut in two at the median of its centres along its longer axis: 16 groups, boxes that
+// barely overlap), unless the runs of 16 along the Z curve -- the grouping before it -- come out strictly cheaper.  Which
+// obstacles reach the exact test does not depend on the grouping: a slot's box contains the cull square of each of its obstacles.
 inline void build_obstacle_slots(WorldTables& t) {
   const int O = (int)t.ox.size();
   const std::vector<double>&ox = t.ox, &oy = t.oy, &ot = t.ot;
@@ -274,6 +278,47 @@ inline void build_obstacle_slots(WorldTables& t) {
   double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;  // bounding box of the obstacle centres
   for (int i = 0; i < O; i++) { x0 = std::min(x0, ox[i]); x1 = std::max(x1, ox[i]); y0 = std::min(y0, oy[i]); y1 = std::max(y1, oy[i]); }
   t.obst_area = (O > 1 && std::isfinite((x1 - x0) * (y1 - y0))) ? (x1 - x0) * (y1 - y0) : 0.0;
+  // the tile's entries from an order: entry k holds obstacle order[k] of the list, padding where that is -1
+  auto place = [&](const std::vector<int>& order) {
+    for (int k = 0; k < NS; k++) {
+      const int i = order[k];
+      if (i < 0) { sx[k] = 0.0; sy[k] = 0.0; st[k] = -1.0; sr[k] = -INFINITY; continue; }
+      sx[k] = ox[i]; sy[k] = oy[i]; st[k] = ot[i];
+      const double rd = ot[i] >= 0.0 ? std::sqrt(ot[i]) * (1.0 + 0x1p-30) + 0x1p-40 : -INFINITY;
+      float rf = (float)rd;
+      if ((double)rf < rd) rf = std::nextafter(rf, INFINITY);
+      sr[k] = rf;
+    }
+  };
+  auto slot_boxes = [&]() {
+    for (int s_ = 0; s_ < 16; s_++) {
+      double b0 = INFINITY, b1 = INFINITY, b2 = -INFINITY, b3 = -INFINITY;
+      for (int k = 16 * s_; k < 16 * s_ + 16; k++) {
+        if (!(sr[k] >= 0.0f) && !std::isnan(sx[k])) continue;  // padding / an obstacle that can never collide
+        const double r = (double)sr[k];
+        if (std::isnan(sx[k]) || std::isnan(sy[k]) || std::isnan(r)) { b0 = b1 = -INFINITY; b2 = b3 = INFINITY; break; }  // never culled
+        b0 = std::min(b0, sx[k] - r); b1 = std::min(b1, sy[k] - r); b2 = std::max(b2, sx[k] + r); b3 = std::max(b3, sy[k] + r);
+      }
+      box[4 * s_] = b0; box[4 * s_ + 1] = b1; box[4 * s_ + 2] = b2; box[4 * s_ + 3] = b3;
+    }
+  };
+  // What a grouping costs: a square of side m set down at random meets a w x h box with a probability that grows as
+  // (w + m)(h + m), summed over the slots.  m = 30 m, the side of a steer's reach square at the planner's default step (its
+  // half-width is a quarter of freq x dist_to_end = 15 m); one fixed figure for both groupings, read from no parameter.  An
+  // empty slot costs nothing; a slot that is never culled (or whose box is not finite) is met by every steer, so those are
+  // counted first and the sum over the others decides between groupings with as many of them
+  auto boxes_cost = [&]() {
+    const double m = 30.0;
+    int unbounded = 0;
+    double sum = 0.0;
+    for (int s_ = 0; s_ < 16; s_++) {
+      const double w = box[4 * s_ + 2] - box[4 * s_], h = box[4 * s_ + 3] - box[4 * s_ + 1];
+      if (w < 0.0 && h < 0.0) continue;
+      if (std::isfinite(w) && std::isfinite(h)) sum += (w + m) * (h + m);
+      else unbounded++;
+    }
+    return std::make_pair(unbounded, sum);
+  };
   if (O <= NS) {
     auto spread = [](uint32_t v) { uint64_t x = v & 0xffff; x = (x | (x << 8)) & 0x00ff00ff; x = (x | (x << 4)) & 0x0f0f0f0f;
                                    x = (x | (x << 2)) & 0x33333333; x = (x | (x << 1)) & 0x55555555; return x; };
@@ -284,24 +329,48 @@ inline void build_obstacle_slots(WorldTables& t) {
       key[i] = {(std::isfinite(fx) && std::isfinite(fy)) ? (spread(qx) | (spread(qy) << 1)) : 0, i};
     }
     std::sort(key.begin(), key.end());
-    for (int k = 0; k < O; k++) {
-      const int i = key[k].second;
-      sx[k] = ox[i]; sy[k] = oy[i]; st[k] = ot[i];
-      const double rd = ot[i] >= 0.0 ? std::sqrt(ot[i]) * (1.0 + 0x1p-30) + 0x1p-40 : -INFINITY;
-      float rf = (float)rd;
-      if ((double)rf < rd) rf = std::nextafter(rf, INFINITY);
-      sr[k] = rf;
+    std::vector<int> morton(NS, -1), median(NS, -1);  // entry k of the tile: the obstacle's index in the list, -1 padding
+    for (int k = 0; k < O; k++) morton[k] = key[k].second;
+    // the median split: idx[cut[g] .. cut[g + 1]) is group g; a cut leaves ceil(n / 2) and floor(n / 2), so 256 obstacles and
+    // fewer end in 16 groups of at most 16.  Sorted by (coordinate, index in the list): the tables are deterministic.  A centre
+    // that is not finite counts for no extent, a NaN sorts last
+    std::vector<int> idx(O), cut = {0, O};
+    for (int i = 0; i < O; i++) idx[i] = i;
+    std::vector<std::pair<double, int>> ck;
+    for (int level = 0; level < 4; level++) {
+      std::vector<int> next;
+      for (size_t g = 0; g + 1 < cut.size(); g++) {
+        const int a = cut[g], n = cut[g + 1] - a;
+        double gx0 = INFINITY, gy0 = INFINITY, gx1 = -INFINITY, gy1 = -INFINITY;
+        for (int k = a; k < a + n; k++) {
+          const double cx = ox[idx[k]], cy = oy[idx[k]];
+          if (std::isfinite(cx)) { gx0 = std::min(gx0, cx); gx1 = std::max(gx1, cx); }
+          if (std::isfinite(cy)) { gy0 = std::min(gy0, cy); gy1 = std::max(gy1, cy); }
+        }
+        const bool along_y = gy1 - gy0 > gx1 - gx0;  // (no finite centre: -inf on that side, never the longer axis)
+        ck.resize(n);
+        for (int k = 0; k < n; k++) {
+          const double c = along_y ? oy[idx[a + k]] : ox[idx[a + k]];
+          ck[k] = {std::isnan(c) ? INFINITY : c, idx[a + k]};
+        }
+        std::sort(ck.begin(), ck.end());
+        for (int k = 0; k < n; k++) idx[a + k] = ck[k].second;
+        next.push_back(a); next.push_back(a + (n + 1) / 2);
+      }
+      next.push_back(O);
+      cut.swap(next);
     }
-  }
-  for (int s_ = 0; s_ < 16; s_++) {
-    double b0 = INFINITY, b1 = INFINITY, b2 = -INFINITY, b3 = -INFINITY;
-    for (int k = 16 * s_; k < 16 * s_ + 16; k++) {
-      if (!(sr[k] >= 0.0f) && !std::isnan(sx[k])) continue;  // padding / an obstacle that can never collide
-      const double r = (double)sr[k];
-      if (std::isnan(sx[k]) || std::isnan(sy[k]) || std::isnan(r)) { b0 = b1 = -INFINITY; b2 = b3 = INFINITY; break; }  // never culled
-      b0 = std::min(b0, sx[k] - r); b1 = std::min(b1, sy[k] - r); b2 = std::max(b2, sx[k] + r); b3 = std::max(b3, sy[k] + r);
-    }
-    box[4 * s_] = b0; box[4 * s_ + 1] = b1; box[4 * s_ + 2] = b2; box[4 * s_ + 3] = b3;
+    for (int s_ = 0; s_ < 16; s_++)
+      for (int k = cut[s_]; k < cut[s_ + 1]; k++) median[16 * s_ + (k - cut[s_])] = idx[k];
+    // never worse than before: the Z-curve runs stay where their boxes are strictly cheaper
+    place(morton);
+    slot_boxes();
+    const auto cost_morton = boxes_cost();
+    place(median);
+    slot_boxes();
+    if (cost_morton < boxes_cost()) { place(morton); slot_boxes(); }
+  } else {
+    slot_boxes();
   }
 }
 
