@@ -55,6 +55,11 @@ GROUP_BEST_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_with_leaf
                              ("cost", "<f8", (4,)), ("length", "<f8")])
 assert GROUP_BEST_DTYPE.itemsize == C.sizeof(RRTGroupBest)
 
+# auvp_replan_record (include/auvplan.h): one AUV's round of the device commit step
+REPLAN_RECORD_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_committed", "<i4"), ("path_len", "<i4"),
+                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("_reserved", "<f8", (2,))])
+assert REPLAN_RECORD_DTYPE.itemsize == 128
+
 MODES = {"timebin": 0, "plantime": 1, "nn": 2}
 # auvp_rrt_episode (include/auvplan.h): one episode's own horizon and habitat list (bit h = habitat h of the world's table)
 EPISODE_DTYPE = np.dtype([("max_traj_time", "<f8"), ("habitat_keep", "<u8")])
@@ -133,6 +138,13 @@ def load():
         L.auvp_rrt_set_episode_grids.argtypes = [vp, C.c_int32, _ip]
         L.auvp_rrt_rerank.argtypes = [vp]
         L.auvp_sf_prob_dev.argtypes = [vp, C.POINTER(C.c_void_p), _ip, _ip, _ip]
+    if hasattr(L, "auvp_replan_begin"):  # (likewise: the device commit step of replanning_batch)
+        _u64p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        L.auvp_replan_begin.argtypes = [vp, C.c_int32, _dp, _u64p, C.c_int32]
+        L.auvp_replan_commit.argtypes = [vp, C.c_int32, _ip, C.c_double, C.c_void_p]
+        L.auvp_replan_traj.argtypes = [vp, _i64p, _dp]
+        L.auvp_replan_commit_courses.argtypes = [vp, C.c_int32, _i64p, _dp, _dp, _u64p, C.c_double, C.c_void_p, _dp]
+        L.auvp_replan_info.argtypes = [vp, _ip, _ip, _i64p, _i64p, _i64p, _dp]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -198,6 +210,16 @@ def episode_limits(n_episodes, max_traj_time, habitat_keep, n_habitats, mode="ti
     allowed = (1 << int(n_habitats)) - 1 if n_habitats < 64 else (1 << 64) - 1
     if habitat_keep is None:
         keep = [allowed] * E
+    elif isinstance(habitat_keep, np.ndarray) and habitat_keep.dtype == np.uint64 and habitat_keep.shape == (E,):
+        # (a fleet's masks as an array: the same check without a Python loop over the episodes)
+        bad = np.flatnonzero(habitat_keep & np.uint64(~allowed & ((1 << 64) - 1)))
+        if len(bad):
+            raise ValueError("episode %d: habitat_keep 0x%x names habitats outside the table of %d"
+                             % (bad[0], int(habitat_keep[bad[0]]), n_habitats))
+        rec = np.zeros(E, dtype=EPISODE_DTYPE)
+        rec["max_traj_time"] = mtt
+        rec["habitat_keep"] = habitat_keep
+        return float(mtt.max()), rec
     else:
         keep = [int(k) for k in np.broadcast_to(np.asarray(habitat_keep, dtype=object), (E,))]
     for e, k in enumerate(keep):
@@ -328,6 +350,7 @@ class Context:
         self.max_iter = 0
         self.world_sizes = {}
         self.n_prob_sets = 0
+        self.n_replan_auvs = 0
         self._world_stamp = 0  # counts set_world / set_habitats: a user that shares the context sees whether its world still stands
 
     def close(self):
@@ -549,6 +572,61 @@ class Context:
         """the winners' courses written to a caller-owned device buffer [offsets[G],7] f64"""
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         self._chk(self.L.auvp_rrt_group_paths_dev(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(out_dev_ptr)))
+
+    # ---- replanning a fleet with the commit step on the device (include/auvplan.h: auvp_replan_*) ----
+    def replan_begin(self, start7, keep0):
+        """a fleet's state on the handle: start7 [N,7] (x, y, theta, v, traj_time_stamp, plan_time_stamp, length), keep0 one
+        habitat bit mask or [N]; an empty trajectory log"""
+        s = _f64(start7, (-1, 7))
+        k = np.ascontiguousarray(np.asarray(keep0, dtype=np.uint64).reshape(-1))
+        if len(k) not in (1, len(s)):
+            raise ValueError("keep0 must be one mask or one per AUV")
+        self._chk(self.L.auvp_replan_begin(self.h, len(s), _p(s), k.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if len(k) == 1 and len(s) != 1 else 0))
+        self.n_replan_auvs = len(s)
+
+    def replan_commit(self, auv_of, round_span, records=True):
+        """one round behind rrt_group_best: group g is AUV auv_of[g]; the winners' first buckets go into the log, the states
+        are updated in HBM.  Returns [n_active] REPLAN_RECORD_DTYPE records (None with records=False)."""
+        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        out = np.zeros(max(len(a), 1), dtype=REPLAN_RECORD_DTYPE) if records else None
+        self._chk(self.L.auvp_replan_commit(self.h, len(a), _p(a, _ip), float(round_span),
+                                            out.ctypes.data_as(C.c_void_p) if records else None))
+        return out[:len(a)] if records else None
+
+    def replan_traj(self):
+        """(row_off [N+1], rows [row_off[N],7]): every AUV's committed trajectory in round order -- the one bulk download"""
+        off = np.zeros(self.n_replan_auvs + 1, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(self.L.auvp_replan_traj(self.h, off.ctypes.data_as(i64p), None))
+        rows = np.zeros((int(off[-1]), 7))
+        if len(rows):
+            self._chk(self.L.auvp_replan_traj(self.h, off.ctypes.data_as(i64p), _p(rows)))
+        return off, rows
+
+    def replan_commit_courses(self, courses, last7, keep, round_span):
+        """probe: rrt_commit_kernel's rule on the caller's courses (a list of [L,7] arrays, L == 0: a state without a winner)
+        and states, against the world's habitat table, one launch.  Returns (records [n], committed rows per state, new
+        last [n,7], new keep [n])."""
+        n = len(courses)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(c) for c in courses])
+        flat = _f64(np.concatenate([_f64(c, (-1, 7)) for c in courses]) if n else [], (-1, 7))
+        last = _f64(last7, (n, 7)).copy()
+        kp = np.array(keep, dtype=np.uint64).reshape(n)
+        out = np.zeros(max(n, 1), dtype=REPLAN_RECORD_DTYPE)
+        rows = np.zeros((max(len(flat), 1), 7))
+        self._chk(self.L.auvp_replan_commit_courses(self.h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(last),
+                                                    kp.ctypes.data_as(C.POINTER(C.c_uint64)), float(round_span),
+                                                    out.ctypes.data_as(C.c_void_p), _p(rows)))
+        return out[:n], [rows[off[i]:off[i] + out[i]["n_committed"]] for i in range(n)], last, kp
+
+    def replan_info(self):
+        """counters since replan_begin: n_auvs, rounds, rows, bytes_to_host (what the replan entry points copied to the host),
+        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, summed)"""
+        a, r = C.c_int32(0), C.c_int32(0)
+        rows, b, bt, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._chk(self.L.auvp_replan_info(self.h, C.byref(a), C.byref(r), C.byref(rows), C.byref(b), C.byref(bt), C.byref(ms)))
+        return dict(n_auvs=a.value, rounds=r.value, rows=rows.value, bytes_to_host=b.value, bytes_traj=bt.value, commit_ms=ms.value)
 
     def tree(self, ep, summary):
         n, npnt = int(summary["n_nodes"]), int(summary["n_points"])

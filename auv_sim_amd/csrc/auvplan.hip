@@ -142,6 +142,8 @@ struct auvp_handle {
   void (*sf_free)(void*) = nullptr;
   void* comm = nullptr;  // RCCL communicator state (gather_host.h)
   void (*comm_free)(void*) = nullptr;
+  void* replan = nullptr;  // a fleet's replanning state and trajectory log (replan_host.h)
+  void (*replan_free)(void*) = nullptr;
   // Pipeline fallback.  The latency kernels (rrt_trio / rrt_duo, prrt_pipe, the paired astar_kernel) are speculative
   // pipelines of several wavefronts per episode whose waits are bounded; an episode whose wait runs out ends with
   // AUVP_ERR_PIPELINE and sets this host-mapped word.  The host then repeats the work on the one-wavefront kernel (same
@@ -344,6 +346,7 @@ void auvp_destroy(auvp_handle* h) {
   if (h->pf && h->pf_free) h->pf_free(h->pf);
   if (h->sf && h->sf_free) h->sf_free(h->sf);
   if (h->comm && h->comm_free) h->comm_free(h->comm);
+  if (h->replan && h->replan_free) h->replan_free(h->replan);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
@@ -1209,3 +1212,4 @@ PrrtState* prrt_of(auvp_handle* h) {
 #include "forecast_host.h"
 #include "compose_host.h"
 #include "gather_host.h"
+#include "replan_host.h"

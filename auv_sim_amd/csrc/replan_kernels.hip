@@ -1,0 +1,145 @@
+// replan_kernels.hip -- the kernels of the device commit step of RRT.replanning_batch (auvp_replan_*, include/auvplan.h) as a
+// translation unit of their own, so that auvplan.hip's device code stays the text it was (leaf_grid_kernels.hip: why).
+//
+//   rrt_commit_kernel   one wavefront per group of the last auvp_rrt_group_best: the winner's course (rrt_final_course) into a
+//                       scratch buffer, the commit rule of replan_commit.h on it, the committed rows into the trajectory log,
+//                       the AUV's state (last, keep) in place, one round record
+//   replan_gather_kernel  the log's pieces into AUV order, for the one download at the end
+//
+// Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define AUVP_LEAF_KERNELS_ELSEWHERE 1  // (rrt_leaf_kernel / rrt_leaf_lim_kernel are auvplan.hip's)
+#include "rrt_explore_kernel.h"
+#include "rrt_group_kernel.h"
+#include "replan_commit.h"
+
+namespace auvp {
+
+// The rule of replan_commit.h on the course of `L` rows at `course`, by one wavefront (all 64 lanes active, every argument the
+// same on every lane).  The lanes take the rows 64 at a time: selection by ballot, the selected rows to `rows_out` at their
+// rank.  The keep fold is serial over the selected rows: for each, lane h tests habitat h and the ballot is the row's
+// inside-mask.  last [7] and *keep are read at the start and written by lane 0 at the end.  Returns the committed rows.
+__device__ inline int replan_commit_wave(const double* __restrict__ course, int L, double* __restrict__ last_io, uint64_t* __restrict__ keep_io,
+                                         double round_span, const double* __restrict__ hab, const double* __restrict__ hab_t, int H,
+                                         double* __restrict__ rows_out, double* last_out7, uint64_t* keep_out) {
+  const int lane = lane_id();
+  double start[REPLAN_ROW], end[REPLAN_ROW];
+#pragma unroll
+  for (int k = 0; k < REPLAN_ROW; k++) start[k] = end[k] = last_io[k];
+  const ReplanBucket b = replan_bucket(start[4], round_span);
+  uint64_t kp = *keep_io;
+  const bool in_table = lane < H;  // (H <= 64: one lane per habitat)
+  int n = 0;
+  for (int c = 0; c < L; c += 64) {
+    const int i = c + lane;
+    const bool valid = i < L;
+    double row[REPLAN_ROW];
+#pragma unroll
+    for (int k = 0; k < REPLAN_ROW; k++) row[k] = valid ? replan_row_field(course, start, i, k) : 0.0;
+    const bool s = valid && replan_selected(b, row[4]);
+    const unsigned long long mask = __ballot(s ? 1 : 0);
+    if (mask == 0) continue;  // (the same on every lane)
+    if (s) {
+      const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+      double* o = rows_out + (size_t)REPLAN_ROW * (size_t)(n + rank);
+#pragma unroll
+      for (int k = 0; k < REPLAN_ROW; k++) o[k] = row[k];
+    }
+    if (kp != 0 && H > 0) {
+      for (unsigned long long m = mask; m != 0 && kp != 0; m &= m - 1) {
+        const int j = __ffsll((long long)m) - 1;
+        const double x = __shfl(row[0], j), y = __shfl(row[1], j);
+        const unsigned long long inside = __ballot((in_table && replan_inside(hab, hab_t, lane, x, y)) ? 1 : 0);
+        kp = replan_keep_fold(kp, inside);
+      }
+    }
+    const int top = 63 - __clzll((long long)mask);
+#pragma unroll
+    for (int k = 0; k < REPLAN_ROW; k++) end[k] = __shfl(row[k], top);
+    n += __popcll(mask);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < REPLAN_ROW; k++) last_io[k] = end[k];
+    *keep_io = kp;
+  }
+#pragma unroll
+  for (int k = 0; k < REPLAN_ROW; k++) last_out7[k] = end[k];
+  *keep_out = kp;
+  return n;
+}
+
+// One wavefront (= one workgroup) per slot.  PRODUCE: the course is the winner's, written here by rrt_final_course (the host
+// reserved slot.path_len rows from its own copy of the group records; a summary that does not agree with that copy commits
+// nothing and reports AUVP_ERR_STATE); otherwise the host put the course there (the probe entry).
+template <bool PRODUCE>
+static __global__ __launch_bounds__(64) void rrt_commit_kernel(RrtBuffers B, ReplanCommitDev A, int n_episodes) {
+  const int g = blockIdx.x;
+  if (g >= A.n_slots) return;
+  const int lane = lane_id();
+  const ReplanSlot slot = A.slots[g];
+  int L = slot.path_len > 0 && slot.winner >= 0 ? slot.path_len : 0;
+  int status = slot.status;
+  double* course = A.course + (size_t)REPLAN_ROW * (size_t)slot.course_off;
+  if (PRODUCE && L > 0) {
+    const int ep = slot.winner;
+    bool ok = ep < n_episodes;
+    if (ok) {
+      const RrtSummary* s = B.summary + ep;
+      ok = s->best_leaf >= 0 && s->best_path_len == L;
+    }
+    if (ok) rrt_final_course(B, ep, course);
+    else { L = 0; status = -4 /* AUVP_ERR_STATE */; }
+  }
+  __syncthreads();  // (the course's rows were written by other lanes of this wavefront)
+  double fin[REPLAN_ROW];
+  uint64_t fin_keep = 0;
+  const int n = replan_commit_wave(course, L, A.last + (size_t)REPLAN_ROW * (size_t)slot.auv, A.keep + slot.auv, A.round_span, A.hab,
+                                   A.hab_t, A.H, A.log + (size_t)REPLAN_ROW * (size_t)slot.log_off, fin, &fin_keep);
+  if (lane == 0) {
+    ReplanRecord r;
+    r.status = status; r.winner = slot.winner; r.n_committed = n; r.path_len = slot.path_len;
+    const double inf = __builtin_inf();
+    r.cost[0] = r.cost[1] = r.cost[2] = r.cost[3] = inf;
+    if (PRODUCE && A.best && slot.winner >= 0) {
+      const RrtGroupBest* gb = A.best + g;
+      r.cost[0] = gb->cost[0]; r.cost[1] = gb->cost[1]; r.cost[2] = gb->cost[2]; r.cost[3] = gb->cost[3];
+    }
+#pragma unroll
+    for (int k = 0; k < REPLAN_ROW; k++) r.last[k] = fin[k];
+    r.keep = fin_keep;
+    r._reserved[0] = r._reserved[1] = 0.0;
+    A.rec[g] = r;
+  }
+}
+
+// segment s: n rows from log row src to trajectory row dst (one wavefront per segment, the doubles spread over the lanes)
+static __global__ __launch_bounds__(64) void replan_gather_kernel(const ReplanSegment* __restrict__ seg, int n_seg, const double* __restrict__ log,
+                                                                  double* __restrict__ out) {
+  const int s = blockIdx.x;
+  if (s >= n_seg) return;
+  const ReplanSegment sg = seg[s];
+  const double* from = log + (size_t)REPLAN_ROW * (size_t)sg.src;
+  double* to = out + (size_t)REPLAN_ROW * (size_t)sg.dst;
+  const int n = sg.n * REPLAN_ROW;
+  for (int i = threadIdx.x; i < n; i += 64) to[i] = from[i];
+}
+
+}  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_commit_launch(const auvp::RrtBuffers* B, const auvp::ReplanCommitDev* A,
+                                                                                       int n_episodes, hipStream_t stream) {
+  if (A->n_slots <= 0) return hipSuccess;
+  if (B) hipLaunchKernelGGL(auvp::rrt_commit_kernel<true>, dim3(A->n_slots), dim3(64), 0, stream, *B, *A, n_episodes);
+  else hipLaunchKernelGGL(auvp::rrt_commit_kernel<false>, dim3(A->n_slots), dim3(64), 0, stream, auvp::RrtBuffers{}, *A, 0);
+  return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_gather_launch(const auvp::ReplanSegment* seg, int n_seg, const double* log,
+                                                                                       double* out, hipStream_t stream) {
+  if (n_seg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(auvp::replan_gather_kernel, dim3(n_seg), dim3(64), 0, stream, seg, n_seg, log, out);
+  return hipGetLastError();
+}

@@ -409,7 +409,7 @@ class RRT:
         return [committed[1:], rounds, total]
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
-                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None):
+                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None, commit="host"):
         """N independent replanning() loops, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
@@ -430,7 +430,13 @@ class RRT:
         continue K streams, so rngs raises ValueError.
 
         shark_of [N]: AUV e plans every round against table shark_of[e] of set_shark_grids, and its whole trajectory's cost
-        is taken against that table (one cost launch per table in use); entry e equals the call on an RRT built with it."""
+        is taken against that table (one cost launch per table in use); entry e equals the call on an RRT built with it.
+
+        commit="device": the step between two rounds runs on the device (rrt_commit_kernel behind the winners' selection) --
+        the courses stay in HBM, one 128-byte record per AUV and round comes back, the host's part of a round is numpy over
+        [N] arrays, and the committed trajectories are downloaded once at the end.  The results equal commit="host" (the
+        default) in every field.  Seeds only (rngs raises ValueError); the ValueError for a horizon that holds no whole bucket
+        is raised before the round is launched."""
         N = len(starts)
         sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
         K = int(trees_per_auv)
@@ -438,6 +444,11 @@ class RRT:
             raise ValueError("trees_per_auv must be >= 1")
         if K > 1 and rngs is not None:
             raise ValueError("rngs cannot be combined with trees_per_auv > 1: one generator cannot continue K streams")
+        if commit not in ("host", "device"):
+            raise ValueError("commit must be 'host' or 'device', not %r" % (commit,))
+        if commit == "device" and rngs is not None:
+            raise ValueError("rngs cannot be combined with commit='device': continuing a generator takes every episode's draw "
+                             "count and a state upload per AUV and round -- the host work this option removes; give seeds")
         horizon_end = list(self.sharkGrid.keys())[-1][1]
         round_span = plan_time_budget + replan_time_interval
         all_habitats = list(habitats)
@@ -445,6 +456,9 @@ class RRT:
         H = len(all_habitats)
         if max_iter is None:
             max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
+        if commit == "device":
+            return self._replanning_batch_device(starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight,
+                                                 max_iter, seeds, as_arrays, K, sets)
         gens = [None] * N     # rngs[e]: the global stream of a sequential call
         streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
         for e in range(N):
@@ -498,23 +512,11 @@ class RRT:
                 keep[e] = new_keep
                 if len(bucket):
                     last[e] = [float(x) for x in bucket[-1]]
-        # the whole trajectory's cost against the ORIGINAL list (:192-195), every AUV in one launch
-        if self._cost_ctx is None:
-            self._cost_ctx = _lib.Context(self._ctx.device)
         done = [e for e in range(N) if traj[e] is not None]
-        costs = {}
-        if done:
-            rows = {e: (np.concatenate(traj[e]) if as_arrays and traj[e] else
-                        np.array([[m.x, m.y, m.theta, m.v, m.traj_time_stamp, m.plan_time_stamp, m.length] for m in traj[e]],
-                                 dtype=np.float64).reshape(-1, 7)) for e in done}
-            # (with shark_of: the AUVs grouped by table, one launch per table in use, each against its own table)
-            for g in ([None] if sets is None else sorted(set(int(sets[e]) for e in done))):
-                grp = done if g is None else [e for e in done if int(sets[e]) == g]
-                self._cost_ctx.set_world(None, hab, None, self._bins, self._cells, self._prob if g is None else self._set_prob[g])
-                out = self._cost_ctx.cost_paths([rows[e][:, [0, 1, 4]] for e in grp], [0] * len(grp), [len(self._bins)] * len(grp),
-                                                [float(rows[e][-1, 4]) if len(rows[e]) else float(last[e][4]) for e in grp],
-                                                [[-3.0, -3.0, -4.0]] * len(grp))
-                costs.update({e: out[i] for i, e in enumerate(grp)})
+        rows = {e: (np.concatenate(traj[e]) if as_arrays and traj[e] else
+                    np.array([[m.x, m.y, m.theta, m.v, m.traj_time_stamp, m.plan_time_stamp, m.length] for m in traj[e]],
+                             dtype=np.float64).reshape(-1, 7)) for e in done}
+        costs = self._replan_costs(done, rows, [s[4] for s in last], hab, sets)
         res = []
         for e in range(N):
             if traj[e] is None:
@@ -531,6 +533,123 @@ class RRT:
                 res.append([traj[e], {k + 1: [b, hl] for k, (b, hl) in enumerate(rounds[e])},
                             [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
                             [all_habitats[h] for h in range(H) if (keep[e] >> h) & 1]])
+        return res
+
+    def _replan_costs(self, done, rows, last_t, hab, sets):
+        """{e: cost [4]} of the whole trajectories rows[e] of the AUVs `done` against the ORIGINAL habitat list (:192-195), every
+        AUV in one launch on the cost-only context (with shark_of: the AUVs grouped by table, one launch per table in use, each
+        against its own table); last_t[e]: the time of an AUV that committed nothing"""
+        if self._cost_ctx is None:
+            self._cost_ctx = _lib.Context(self._ctx.device)
+        costs = {}
+        if done:
+            for g in ([None] if sets is None else sorted(set(int(sets[e]) for e in done))):
+                grp = done if g is None else [e for e in done if int(sets[e]) == g]
+                self._cost_ctx.set_world(None, hab, None, self._bins, self._cells, self._prob if g is None else self._set_prob[g])
+                out = self._cost_ctx.cost_paths([rows[e][:, [0, 1, 4]] for e in grp], [0] * len(grp), [len(self._bins)] * len(grp),
+                                                [float(rows[e][-1, 4]) if len(rows[e]) else float(last_t[e]) for e in grp],
+                                                [[-3.0, -3.0, -4.0]] * len(grp))
+                costs.update({e: out[i] for i, e in enumerate(grp)})
+        return costs
+
+    def _replanning_batch_device(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter,
+                                 seeds, as_arrays, K, sets):
+        """replanning_batch with commit="device": per round one prepare + run, the winners' selection, and rrt_commit_kernel
+        (Context.replan_commit); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
+        drawing each active AUV's K round seeds from its random.Random."""
+        N, H = len(starts), len(all_habitats)
+        if seeds is None or len(seeds) != N or any(s is None for s in seeds):
+            raise ValueError("AUV %d has neither a seed nor a generator"
+                             % (0 if seeds is None or len(seeds) != N else [s is None for s in seeds].index(True)))
+        streams = [random.Random(s) for s in seeds]
+        last = np.array([[float(m.x), float(m.y), float(m.theta), float(getattr(m, "v", 0.0) or 0.0), float(m.traj_time_stamp),
+                          float(m.plan_time_stamp), float(m.length)] for m in starts], dtype=np.float64).reshape(N, 7)
+        keep = np.full(N, (1 << H) - 1, dtype=np.uint64)
+        ttl = np.full(N, float(traj_time_length))
+        alive = np.ones(N, dtype=bool)
+        ctx = self._ctx
+        ctx.set_habitats(hab)  # (the whole list: every episode's own list is its keep mask over this table)
+        ctx.replan_begin(last, keep)
+        self._batch = None  # (rerank follows an exploring_batch only)
+        log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
+        while True:
+            act = np.flatnonzero(alive & (last[:, 4] + round_span < horizon_end))
+            if len(act) == 0:
+                break
+            t_now = last[act, 4]
+            clip = ttl[act] + t_now > horizon_end  # stays clipped for the later rounds too (:76-77)
+            ttl[act[clip]] = horizon_end - t_now[clip]
+            mtt = ttl[act] + t_now
+            short = np.floor(mtt / round_span) < 1  # (first_bucket_commit's ValueError, from the host's numbers, before the launch)
+            if short.any():
+                raise ValueError("max_traj_time %r holds no shark-interval bucket of %r" % (float(mtt[np.argmax(short)]), round_span))
+            seed_arg = np.array([streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
+            ctx.rrt_explore_batch(np.repeat(last[act][:, [0, 1, 2, 4, 5, 6]], K, axis=0), seed_arg, int(max_iter), mode="timebin",
+                                  freq=self.freq, bin_interval=5, v=2, max_traj_time=np.repeat(mtt, K), weights=weight,
+                                  dist_to_end=self.dist_to_end, diff_max=self.diff_max, min_dist=0.5, max_plan_time=float(max_iter),
+                                  habitat_keep=np.repeat(keep[act], K), summaries=False,
+                                  shark_set=None if sets is None else np.repeat(sets[act], K))
+            best = ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
+            bad = best["status"] < 0
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise _lib.AuvpError(int(best[i]["status"]), ("a tree of AUV %d failed on the device (status %d)" if K > 1 else
+                                                              "AUV %d failed on the device (status %d)") % (act[i], int(best[i]["status"])))
+            rec = ctx.replan_commit(act, round_span)
+            bad = rec["status"] < 0
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise _lib.AuvpError(int(rec[i]["status"]), "AUV %d: the commit step failed on the device (status %d)" % (act[i], int(rec[i]["status"])))
+            won = rec["winner"] >= 0
+            alive[act[~won]] = False  # no qualifying leaf: the sequential call would raise TypeError
+            log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won]))
+            last[act] = rec["last"]
+            keep[act] = rec["keep"]
+        row_off, rows_all = ctx.replan_traj()
+        done = [int(e) for e in np.flatnonzero(alive)]
+        rows = {e: rows_all[row_off[e]:row_off[e + 1]] for e in done}
+        costs = self._replan_costs(done, rows, last[:, 4], hab, sets)
+        # the rounds of every AUV, in round order: one stable sort of all the rounds' records by AUV
+        if log:
+            auv = np.concatenate([x[0] for x in log])
+            order = np.argsort(auv, kind="stable")
+            r_rec = np.concatenate([x[1] for x in log])[order]
+            r_keep = np.concatenate([x[2] for x in log])[order]
+            r_mtt = np.concatenate([x[3] for x in log])[order]
+            r_tree = np.concatenate([x[4] for x in log])[order].astype(np.int64)
+            first = np.searchsorted(auv[order], np.arange(N + 1))
+        else:
+            r_rec, r_keep, r_mtt, r_tree = np.zeros(0, _lib.REPLAN_RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0, np.int64)
+            first = np.zeros(N + 1, dtype=np.int64)
+        res = []
+        for e in range(N):
+            if not alive[e]:
+                res.append(None)
+                continue
+            a, b = int(first[e]), int(first[e + 1])
+            lens = r_rec["n_committed"][a:b].astype(np.int64)
+            if as_arrays:
+                res.append(dict(traj=rows[e], round_len=lens, round_keep=r_keep[a:b].copy(), round_max_traj_time=r_mtt[a:b].copy(),
+                                round_cost=r_rec["cost"][a:b].reshape(-1, 4).copy(), round_tree=r_tree[a:b].copy(),
+                                keep=int(keep[e]), cost=costs[e]))
+                continue
+            # objects: each round's first row is the previous round's last object (the start object in round 1), the rest are
+            # new -- what _materialise_course makes of the course on the host route
+            traj, rounds, prev, at = [], {}, starts[e], 0
+            for k, n in enumerate(lens):
+                objs = [prev] + [Motion_plan_state(float(r[0]), float(r[1]), theta=float(r[2]), v=float(r[3]), traj_time_stamp=float(r[4]),
+                                                   plan_time_stamp=float(r[5]), length=float(r[6])) for r in rows[e][at + 1:at + n]]
+                if n == 0:
+                    objs = []
+                at += int(n)
+                traj.extend(objs)
+                kb = int(r_keep[a + k])
+                rounds[k + 1] = [objs, [all_habitats[h] for h in range(H) if (kb >> h) & 1]]
+                if objs:
+                    prev = objs[-1]
+            c = costs[e]
+            res.append([traj, rounds, [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
+                        [all_habitats[h] for h in range(H) if (int(keep[e]) >> h) & 1]])
         return res
 
     def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):

@@ -204,6 +204,54 @@ int auvp_rrt_set_episode_grids(auvp_handle* h, int32_t n_episodes, const int32_t
  * the batch was prepared. */
 int auvp_rrt_rerank(auvp_handle* h);
 
+/* Replanning a fleet with the step between two rounds on the device (RRT.replanning_batch, commit="device").  The reference's
+ * host step (path_planning/rrt_dubins.py:82-87: the first bucket of splitPath, then removeHabitat) is one pure function,
+ * csrc/replan_commit.h, and rrt_commit_kernel applies it to every group's winner behind auvp_rrt_group_best: the winners'
+ * courses never leave HBM, the committed rows go into a trajectory log the handle owns, and only one fixed-size record per
+ * AUV and round crosses the bus.  An AUV's state: last [7] (x, y, theta, v, traj_time_stamp, plan_time_stamp, length) and keep
+ * (bit h: habitat h of the world's table is still on its list).  The rule, for a course c[0..L-1] of 7 doubles as
+ * auvp_rrt_paths writes it: row 0 is replaced by last; lo = last[4] + 0 * round_span, hi = last[4] + 1 * round_span; row i is
+ * committed iff lo <= t_i <= hi (a NaN: never), in course order; every committed row, in order, removes from keep the lowest
+ * kept habitat that contains it (sqrt(dx*dx + dy*dy) <= size, no contraction); last becomes the last committed row. */
+typedef struct {
+  int32_t status;      /* the group record's status (auvp_rrt_group_best); AUVP_ERR_STATE: the batch's summaries no longer
+                        * agree with the group records the space was reserved from -- nothing was committed */
+  int32_t winner;      /* episode of the batch whose course was committed, -1: none (nothing committed, state unchanged) */
+  int32_t n_committed; /* rows appended to the AUV's trajectory */
+  int32_t path_len;    /* rows of the winner's course */
+  double cost[4];      /* the winner's best_cost (inf without one) */
+  double last[7];      /* the AUV's state after the round */
+  uint64_t keep;
+  double _reserved[2];
+} auvp_replan_record; /* 128 bytes */
+/* A fleet's state on the handle: last = start7 [n_auvs,7], keep = keep0 [n_auvs] (keep_is_shared != 0: keep0[0] for everyone),
+ * an empty log, zeroed counters.  It survives auvp_rrt_prepare*, auvp_rrt_run, auvp_world_set_habitats and
+ * auvp_world_set_prob_sets; a new auvp_replan_begin or auvp_destroy drops it. */
+int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, const uint64_t* keep0, int32_t keep_is_shared);
+/* One round: group g of the last auvp_rrt_group_best is AUV auv_of[g].  One launch (rrt_commit_kernel, one wavefront per
+ * group); the round's log space is reserved from the host's copy of the group records before it.  A group without a winner, or
+ * whose status is < 0, commits nothing.  out [n_active] may be NULL.  AUVP_ERR_STATE: no auvp_replan_begin, no batch that has
+ * run, or no auvp_rrt_group_best for that batch.  AUVP_ERR_ARG: n_active is not the number of groups, an index outside
+ * [0, n_auvs), an AUV named twice, round_span not > 0.  A call that fails launches nothing and changes no state. */
+int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of /* [n_active] */, double round_span,
+                       auvp_replan_record* out /* [n_active], may be NULL */);
+/* Every AUV's whole committed trajectory, in round order: AUV a's rows are row_off[a] .. row_off[a+1]-1 of rows [*,7].  The only
+ * bulk copy to the host (one gather launch, one copy of rows * 56 bytes).  rows == NULL: row_off [n_auvs+1] alone, to size the
+ * buffer.  AUVP_ERR_STATE without auvp_replan_begin. */
+int auvp_replan_traj(auvp_handle* h, int64_t* row_off /* [n_auvs+1] */, double* rows /* may be NULL */);
+/* Probe: rrt_commit_kernel's rule on the caller's courses and states, against the handle's habitat table (one launch, one
+ * wavefront per state).  State i's course is rows course_off[i] .. course_off[i+1]-1 of courses [*,7] (none: a state without a
+ * winner); last7 [n,7] and keep [n] are updated in place; out [n] gets the records (winner 0 or -1, cost inf) and rows_out [*,7]
+ * state i's committed rows from row course_off[i] on.  The fleet's state of auvp_replan_begin is not touched. */
+int auvp_replan_commit_courses(auvp_handle* h, int32_t n_states, const int64_t* course_off /* [n_states+1] */,
+                               const double* courses, double* last7, uint64_t* keep, double round_span, auvp_replan_record* out,
+                               double* rows_out);
+/* Counters since auvp_replan_begin (each pointer may be NULL): the fleet's size (0: none), rounds committed, rows in the log,
+ * the bytes the auvp_replan_* entry points have copied to the host, the part of those that auvp_replan_traj copied, and
+ * rrt_commit_kernel's time summed over the rounds (HIP events, milliseconds). */
+int auvp_replan_info(auvp_handle* h, int32_t* n_auvs, int32_t* rounds, int64_t* rows, int64_t* bytes_to_host, int64_t* bytes_traj,
+                     double* commit_ms);
+
 /* ---------------------------------------------------------------------------------------------
  * Planner_RRT (gym_rrt/envs/rrt_dubins.py:34): goal-directed RRT driven by the RL environment.
  * Obstacles come from auvp_world_set (list order matters, :445-451); everything else is here.

@@ -1,13 +1,18 @@
 """RRT.replanning_batch throughput (profiles/replan_batch_probe.md).
 
-    python tools/replan_batch_probe.py [--sizes 256,1024,4096] [--iters 2000] [--seq 4]
+    python tools/replan_batch_probe.py [--sizes 256,1024,4096] [--iters 2000] [--seq 4] [--commit host|device] [--runs 1]
 
 For N AUVs on a G13-style world (synth.make_world(seed=1, n_obstacles=64), the world of tests/golden/g13_replan_a; plan budget
 2, horizon 150 s, replan interval 98 s) and `iters` iterations per round: every round's launch (AUVs still planning, expansions
 per second of the expansion + leaf pass) and the wall time of the whole batch.  Then a few AUVs through the sequential
 RRT.replanning (wall time per AUV, for the ratio), and at each N the same parameters as one uniform batch through the
 per-episode-limits kernel and through plain rrt_explore_kernel (options ROWS = DUO = TRIO = 0): the cost of reading the
-limits per episode.  One JSON line per measurement."""
+limits per episode.  One JSON line per measurement.
+
+--commit device: the step between two rounds on the device (rrt_commit_kernel; profiles/replan_device_commit.md); the line
+then also carries the commit kernel's own time and, from replan_info, the bytes per round that came back to the host and the
+one trajectory download.  --runs R: the batch R times after the warm-up, one line each (the uniform-batch and sequential parts
+only with --commit host)."""
 import argparse
 import json
 import math
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--sizes", default="256,1024,4096")
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--seq", type=int, default=4)
+    ap.add_argument("--commit", choices=("host", "device"), default="host")
+    ap.add_argument("--runs", type=int, default=1)
     a = ap.parse_args()
     budget, length, interval = 2.0, 150.0, 98.0
     w = synth.make_world(seed=1, n_obstacles=64)
@@ -73,25 +80,37 @@ def main():
 
     def timed(*args, **kw):
         s = run(*args, **kw)
-        launches.append((len(s), int(s["iters_run"].sum()), rrt._ctx.last_kernel_ms(), rrt._ctx.last_rrt_kernel()))
+        # (the device route leaves the summaries in HBM: every episode runs its whole budget, args[2] iterations)
+        n, it = (len(s), int(s["iters_run"].sum())) if s is not None else (len(args[0]), len(args[0]) * int(args[2]))
+        launches.append((n, it, rrt._ctx.last_kernel_ms(), rrt._ctx.last_rrt_kernel()))
         return s
     rrt._ctx.rrt_explore_batch = timed
     for N in [int(x) for x in a.sizes.split(",")]:
         starts = starts_near(w, N, N)
         seeds = list(range(1, N + 1))
         rrt.replanning_batch(starts[:8], habitats, budget, length, interval, [-3, -3, -4], max_iter=a.iters, seeds=seeds[:8],
-                             as_arrays=True)  # warm-up (code objects, buffers)
-        launches.clear()
-        t0 = time.perf_counter()
-        res = rrt.replanning_batch(starts, habitats, budget, length, interval, [-3, -3, -4], max_iter=a.iters, seeds=seeds,
-                                   as_arrays=True)
-        wall = time.perf_counter() - t0
-        rounds = [dict(auvs=n, expansions=it, ms=round(ms, 3), mexp_s=round(it / ms / 1e3, 1), kernel=k) for n, it, ms, k in launches]
-        exp = sum(r["expansions"] for r in rounds)
-        print(json.dumps(dict(probe="replanning_batch", auvs=N, iters=a.iters, wall_s=round(wall, 3),
-                              kernel_ms=round(sum(r["ms"] for r in rounds), 3), expansions=exp,
-                              mexp_s_kernel=round(exp / sum(r["ms"] for r in rounds) / 1e3, 1),
-                              mexp_s_wall=round(exp / wall / 1e6, 2), none=sum(r is None for r in res), rounds=rounds)), flush=True)
+                             as_arrays=True, commit=a.commit)  # warm-up (code objects, buffers)
+        for _ in range(a.runs):
+            launches.clear()
+            t0 = time.perf_counter()
+            res = rrt.replanning_batch(starts, habitats, budget, length, interval, [-3, -3, -4], max_iter=a.iters, seeds=seeds,
+                                       as_arrays=True, commit=a.commit)
+            wall = time.perf_counter() - t0
+            rounds = [dict(auvs=n, expansions=it, ms=round(ms, 3), mexp_s=round(it / ms / 1e3, 1), kernel=k) for n, it, ms, k in launches]
+            exp = sum(r["expansions"] for r in rounds)
+            extra = {}
+            if a.commit == "device":
+                info = rrt._ctx.replan_info()
+                extra = dict(commit_kernel_ms=round(info["commit_ms"], 3), commit_rounds=info["rounds"], rows=info["rows"],
+                             bytes_traj=info["bytes_traj"],
+                             bytes_per_round=round((info["bytes_to_host"] - info["bytes_traj"]) / max(info["rounds"], 1), 1))
+            print(json.dumps(dict(probe="replanning_batch", commit=a.commit, auvs=N, iters=a.iters, wall_s=round(wall, 3),
+                                  kernel_ms=round(sum(r["ms"] for r in rounds), 3), expansions=exp,
+                                  mexp_s_kernel=round(exp / sum(r["ms"] for r in rounds) / 1e3, 1),
+                                  mexp_s_wall=round(exp / wall / 1e6, 2), none=sum(r is None for r in res), **extra,
+                                  rounds=rounds)), flush=True)
+        if a.commit == "device":
+            continue
         # the same parameters as one uniform batch: per-episode-limits kernel vs plain rrt_explore_kernel
         ctx = _lib.Context(0)
         ctx.set_world(w["obstacles"], w["habitats"], w["polygon"], w["bins"], w["cells"], w["prob"])
@@ -112,7 +131,7 @@ def main():
                               lim_over_plain=round(out["lim"]["ms"] / out["plain"]["ms"], 4))), flush=True)
         ctx.close()
     # sequential replanning, a few AUVs: wall time per AUV
-    if a.seq:
+    if a.seq and a.commit == "host":
         starts = starts_near(w, a.seq, 7)
         rrt.replanning(starts[0], list(habitats), budget, length, interval, [-3, -3, -4], max_iter=a.iters, seed=1)  # warm-up
         t0 = time.perf_counter()
