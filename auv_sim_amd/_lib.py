@@ -145,6 +145,9 @@ def load():
         L.auvp_replan_traj.argtypes = [vp, _i64p, _dp]
         L.auvp_replan_commit_courses.argtypes = [vp, C.c_int32, _i64p, _dp, _dp, _u64p, C.c_double, C.c_void_p, _dp]
         L.auvp_replan_info.argtypes = [vp, _ip, _ip, _i64p, _i64p, _i64p, _dp]
+    if hasattr(L, "auvp_replan_set_teams"):  # (likewise: teams that share one habitat list)
+        L.auvp_replan_set_teams.argtypes = [vp, C.c_int32, _ip]
+        L.auvp_replan_team_fold.argtypes = [vp, C.c_int32, _ip, C.POINTER(C.c_uint64)]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -584,6 +587,26 @@ class Context:
         self._chk(self.L.auvp_replan_begin(self.h, len(s), _p(s), k.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if len(k) == 1 and len(s) != 1 else 0))
         self.n_replan_auvs = len(s)
 
+    def replan_set_teams(self, team_of):
+        """the fleet's teams: team_of [N] int labels (equal labels >= 0: one team, < 0: on its own) or None to clear them.  From
+        then on every replan_commit ends with replan_team_kernel: each member's keep, in the state and in the round's records,
+        is the AND of its team's masks."""
+        if team_of is None:
+            self._chk(self.L.auvp_replan_set_teams(self.h, self.n_replan_auvs, None))
+            return
+        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
+        self._chk(self.L.auvp_replan_set_teams(self.h, len(t), _p(t, _ip)))
+
+    def replan_team_fold(self, team_of, keep):
+        """probe: replan_team_kernel on the caller's labels [n] and keep masks [n], one launch; returns the folded masks [n]
+        (uint64).  Needs no world and no fleet, and touches neither."""
+        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
+        kp = np.array(keep, dtype=np.uint64).reshape(-1)
+        if len(kp) != len(t):
+            raise ValueError("team_of has %d entries, keep %d" % (len(t), len(kp)))
+        self._chk(self.L.auvp_replan_team_fold(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return kp
+
     def replan_commit(self, auv_of, round_span, records=True):
         """one round behind rrt_group_best: group g is AUV auv_of[g]; the winners' first buckets go into the log, the states
         are updated in HBM.  Returns [n_active] REPLAN_RECORD_DTYPE records (None with records=False)."""
@@ -622,7 +645,7 @@ class Context:
 
     def replan_info(self):
         """counters since replan_begin: n_auvs, rounds, rows, bytes_to_host (what the replan entry points copied to the host),
-        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, summed)"""
+        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, with teams replan_team_kernel's too, summed)"""
         a, r = C.c_int32(0), C.c_int32(0)
         rows, b, bt, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         self._chk(self.L.auvp_replan_info(self.h, C.byref(a), C.byref(r), C.byref(rows), C.byref(b), C.byref(bt), C.byref(ms)))

@@ -1,13 +1,16 @@
 // replan_host.h -- host side of the device commit step of RRT.replanning_batch (auvp_replan_*, include/auvplan.h): the fleet's
-// state on the handle (last [n,7], keep [n], the trajectory log), the launch of rrt_commit_kernel (replan_kernels.hip) behind
-// auvp_rrt_group_best, the one download at the end, and the probe entry that runs the kernel's rule on the caller's courses.
+// state on the handle (last [n,7], keep [n], the trajectory log, the teams), the launch of rrt_commit_kernel (replan_kernels.hip)
+// behind auvp_rrt_group_best and of replan_team_kernel behind it where the fleet has teams, the one download at the end, and the
+// probe entries that run the kernels' rules on the caller's courses and masks.
 // Every index the kernel uses is computed here from host data: the group records' host copy (h->group_best) sizes the course
 // scratch and the round's log space before the launch.
 // Included at the end of auvplan.hip.
 #ifndef AUVP_REPLAN_HOST_H
 #define AUVP_REPLAN_HOST_H
 #include "replan_commit.h"
+#include "replan_teams.h"
 
+extern "C" hipError_t auvpi_replan_team_launch(const auvp::ReplanTeamDev* T, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_commit_launch(const auvp::RrtBuffers* B, const auvp::ReplanCommitDev* A, int n_episodes, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_gather_launch(const auvp::ReplanSegment* seg, int n_seg, const double* log, double* out, hipStream_t stream);
 
@@ -26,7 +29,10 @@ struct ReplanState {
   std::vector<Piece> pieces;               // in round order
   std::vector<auvp::ReplanRecord> rec_host;
   long long bytes_to_host = 0, bytes_traj = 0;
-  double commit_ms = 0.0;                  // rrt_commit_kernel's time, summed over the rounds
+  double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's), summed over the rounds
+  // the fleet's teams (auvp_replan_set_teams): the CSR of replan_teams.h in HBM; n_teams == 0: none, nothing more is launched
+  int n_teams = 0;
+  DevBuf team_off, team_members, slot_of;
 };
 
 ReplanState* replan_of(auvp_handle* h) {
@@ -53,18 +59,30 @@ int replan_log_reserve(auvp_handle* h, ReplanState& S, long long rows) {
   return AUVP_OK;
 }
 
-// rrt_commit_kernel on the slots, timed; the records come back into S.rec_host
+// rrt_commit_kernel on the slots and, with `teams`, replan_team_kernel on the fleet's teams behind it, timed together; the
+// records come back into S.rec_host
 int replan_launch(auvp_handle* h, ReplanState& S, const auvp::RrtBuffers* B, auvp::ReplanCommitDev& A, const std::vector<auvp::ReplanSlot>& slots,
-                  double* ms_out) {
+                  double* ms_out, bool teams = false) {
   int rc;
   if ((rc = upload(h, S.slots, slots.data(), slots.size()))) return rc;
   HIPCHK(h, S.rec.reserve(slots.size() * sizeof(auvp::ReplanRecord)));
+  auvp::ReplanTeamDev T{};
+  std::vector<int32_t> slot_of;  // (lives until the stream is waited for below)
+  if (teams) {
+    slot_of.assign((size_t)S.n_auvs, -1);
+    for (size_t g = 0; g < slots.size(); g++) slot_of[(size_t)slots[g].auv] = (int32_t)g;  // (auv: checked against [0, n_auvs) by the caller)
+    if ((rc = upload(h, S.slot_of, slot_of.data(), slot_of.size()))) return rc;
+    T.n_teams = S.n_teams;
+    T.team_off = S.team_off.as<int32_t>(); T.members = S.team_members.as<int32_t>(); T.slot_of = S.slot_of.as<int32_t>();
+    T.keep = A.keep; T.rec = S.rec.as<auvp::ReplanRecord>();
+  }
   A.n_slots = (int32_t)slots.size();
   A.slots = S.slots.as<auvp::ReplanSlot>();
   A.rec = S.rec.as<auvp::ReplanRecord>();
   A.H = h->W.n_habitats; A.hab = h->W.hab; A.hab_t = h->W.hab_t;
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, auvpi_replan_commit_launch(B, &A, h->E, h->stream));
+  if (teams) HIPCHK(h, auvpi_replan_team_launch(&T, h->stream));
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   S.rec_host.resize(slots.size());
   HIPCHK(h, hipMemcpyAsync(S.rec_host.data(), S.rec.p, slots.size() * sizeof(auvp::ReplanRecord), hipMemcpyDeviceToHost, h->stream));
@@ -98,7 +116,58 @@ int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, cons
   S.pieces.clear();
   S.bytes_to_host = S.bytes_traj = 0;
   S.commit_ms = 0.0;
+  S.n_teams = 0;  // (the teams were the old fleet's)
   S.n_auvs = n_auvs;
+  return AUVP_OK;
+}
+
+int auvp_replan_set_teams(auvp_handle* h, int32_t n_auvs, const int32_t* team_of) {
+  if (!h) return AUVP_ERR_ARG;
+  ReplanState* Sp = static_cast<ReplanState*>(h->replan);
+  if (!Sp || Sp->n_auvs < 1) return fail(h, AUVP_ERR_STATE, "auvp_replan_begin not called");
+  ReplanState& S = *Sp;
+  if (n_auvs != S.n_auvs) return fail(h, AUVP_ERR_ARG, "n_auvs %d, the fleet has %d", n_auvs, S.n_auvs);
+  if (!team_of) { S.n_teams = 0; return AUVP_OK; }
+  const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
+  if (csr.n_teams() == 0) { S.n_teams = 0; return AUVP_OK; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // into buffers of their own, swapped in once both tables are there: a call that fails leaves the teams as they were
+  DevBuf off, mem;
+  int rc;
+  if ((rc = upload(h, off, csr.team_off.data(), csr.team_off.size()))) return rc;
+  if ((rc = upload(h, mem, csr.members.data(), csr.members.size()))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::swap(S.team_off.p, off.p); std::swap(S.team_off.cap, off.cap);
+  std::swap(S.team_members.p, mem.p); std::swap(S.team_members.cap, mem.cap);
+  S.n_teams = csr.n_teams();
+  return AUVP_OK;
+}
+
+int auvp_replan_team_fold(auvp_handle* h, int32_t n, const int32_t* team_of, uint64_t* keep_io) {
+  if (!h) return AUVP_ERR_ARG;
+  if (n < 1 || !team_of || !keep_io) return fail(h, AUVP_ERR_ARG, "need n >= 1, the labels and the keep masks");
+  const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n);
+  if (csr.n_teams() == 0) return AUVP_OK;  // (nobody has a teammate: nothing to fold)
+  HIPCHK(h, hipSetDevice(h->device));
+  // the probe's own buffers: the fleet's state and counters (auvp_replan_begin) stay as they are
+  DevBuf d_keep, d_off, d_mem;
+  int rc;
+  if ((rc = upload(h, d_keep, keep_io, (size_t)n))) return rc;
+  if ((rc = upload(h, d_off, csr.team_off.data(), csr.team_off.size()))) return rc;
+  if ((rc = upload(h, d_mem, csr.members.data(), csr.members.size()))) return rc;
+  auvp::ReplanTeamDev T{};
+  T.n_teams = csr.n_teams();
+  T.team_off = d_off.as<int32_t>(); T.members = d_mem.as<int32_t>();
+  T.keep = d_keep.as<uint64_t>();
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, auvpi_replan_team_launch(&T, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(keep_io, d_keep.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms; h->last_grid = (T.n_teams + auvp::REPLAN_TEAM_WAVES - 1) / auvp::REPLAN_TEAM_WAVES;
+  h->last_block = auvp::REPLAN_TEAM_WAVES * 64; h->last_lds = 0;
   return AUVP_OK;
 }
 
@@ -141,7 +210,7 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
   A.last = S.last.as<double>(); A.keep = S.keep.as<uint64_t>();
   A.round_span = round_span;
   double ms = 0.0;
-  if ((rc = replan_launch(h, S, &h->B, A, slots, &ms))) return rc;
+  if ((rc = replan_launch(h, S, &h->B, A, slots, &ms, S.n_teams > 0))) return rc;
   for (int g = 0; g < G; g++) {
     const auvp::ReplanRecord& r = S.rec_host[(size_t)g];
     const int n = r.n_committed > 0 && r.n_committed <= slots[(size_t)g].path_len ? r.n_committed : 0;

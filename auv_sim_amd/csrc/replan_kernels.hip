@@ -5,6 +5,8 @@
 //                       scratch buffer, the commit rule of replan_commit.h on it, the committed rows into the trajectory log,
 //                       the AUV's state (last, keep) in place, one round record
 //   replan_gather_kernel  the log's pieces into AUV order, for the one download at the end
+//   replan_team_kernel  one wavefront per team (replan_teams.h): every member's keep becomes the AND of the members' masks,
+//                       in the state array and in the round's records
 //
 // Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
 #include <hip/hip_runtime.h>
@@ -14,6 +16,7 @@
 #include "rrt_explore_kernel.h"
 #include "rrt_group_kernel.h"
 #include "replan_commit.h"
+#include "replan_teams.h"
 
 namespace auvp {
 
@@ -127,7 +130,49 @@ static __global__ __launch_bounds__(64) void replan_gather_kernel(const ReplanSe
   for (int i = threadIdx.x; i < n; i += 64) to[i] = from[i];
 }
 
+// wave-wide AND of a 64-bit word (identical on every lane on return; all 64 lanes active): four rotate steps inside the 16-lane
+// rows on the DPP path, each half of the word on its own, then the four row results -- as wave_min_i32
+__device__ __forceinline__ uint64_t wave_and_u64(uint64_t v) {
+  int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+  lo &= __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xf, 0xf, false); hi &= __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xf, 0xf, false);
+  lo &= __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xf, 0xf, false); hi &= __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xf, 0xf, false);
+  lo &= __builtin_amdgcn_update_dpp(0, lo, 0x122, 0xf, 0xf, false); hi &= __builtin_amdgcn_update_dpp(0, hi, 0x122, 0xf, 0xf, false);
+  lo &= __builtin_amdgcn_update_dpp(0, lo, 0x121, 0xf, 0xf, false); hi &= __builtin_amdgcn_update_dpp(0, hi, 0x121, 0xf, 0xf, false);
+  const int l = __builtin_amdgcn_readlane(lo, 0) & __builtin_amdgcn_readlane(lo, 16) & __builtin_amdgcn_readlane(lo, 32) &
+                __builtin_amdgcn_readlane(lo, 48);
+  const int h = __builtin_amdgcn_readlane(hi, 0) & __builtin_amdgcn_readlane(hi, 16) & __builtin_amdgcn_readlane(hi, 32) &
+                __builtin_amdgcn_readlane(hi, 48);
+  return ((uint64_t)(uint32_t)h << 32) | (uint32_t)l;
+}
+
+// The team fold of replan_teams.h: one wavefront per team of the CSR.  Lane l ANDs the masks of members l, l + 64, ... (a lane
+// without a member holds all ones), the wavefront ANDs the lanes, and a second strided pass stores the team's list into every
+// member's keep and, where the member has a record in this round, into that record.  Teams are disjoint: plain stores, no
+// atomics.  Runs behind rrt_commit_kernel on the same stream, so every commit of the round is in keep when it reads.
+static __global__ __launch_bounds__(REPLAN_TEAM_WAVES * 64) void replan_team_kernel(ReplanTeamDev T) {
+  const int t = (int)blockIdx.x * REPLAN_TEAM_WAVES + (int)(threadIdx.x >> 6);
+  if (t >= T.n_teams) return;  // (the whole wavefront)
+  const int lane = lane_id();
+  const int lo = T.team_off[t], hi = T.team_off[t + 1];
+  const uint64_t k = wave_and_u64(replan_team_and(T.keep, T.members, lo + lane, hi, 64));
+  for (int i = lo + lane; i < hi; i += 64) {
+    const int m = T.members[i];
+    T.keep[m] = k;
+    if (T.slot_of) {
+      const int s = T.slot_of[m];
+      if (s >= 0) T.rec[s].keep = k;
+    }
+  }
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_team_launch(const auvp::ReplanTeamDev* T, hipStream_t stream) {
+  if (T->n_teams <= 0) return hipSuccess;
+  const int blocks = (T->n_teams + auvp::REPLAN_TEAM_WAVES - 1) / auvp::REPLAN_TEAM_WAVES;
+  hipLaunchKernelGGL(auvp::replan_team_kernel, dim3(blocks), dim3(auvp::REPLAN_TEAM_WAVES * 64), 0, stream, *T);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_commit_launch(const auvp::RrtBuffers* B, const auvp::ReplanCommitDev* A,
                                                                                        int n_episodes, hipStream_t stream) {

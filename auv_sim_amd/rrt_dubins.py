@@ -133,6 +133,61 @@ def shark_set_indices(shark_of, n, n_sets, timebin=True):
     return out
 
 
+def team_labels(teams, n):
+    """replanning_batch's teams -> [n] int32 labels, checked without a device: AUVs with the same label >= 0 form a team, a
+    label < 0 is an AUV on its own; labels need not be dense.  ValueError for a wrong length, a bool, a value that is no integer
+    or one outside int32."""
+    lab = list(teams)
+    if len(lab) != n:
+        raise ValueError("teams has %d entries, expected %d" % (len(lab), n))
+    out = np.zeros(n, dtype=np.int32)
+    for i, t in enumerate(lab):
+        try:
+            ok = not isinstance(t, (bool, np.bool_)) and int(t) == t
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("teams[%d] = %r is not an integer" % (i, t))
+        if not -2 ** 31 <= int(t) < 2 ** 31:
+            raise ValueError("teams[%d] = %d outside int32" % (i, int(t)))
+        out[i] = int(t)
+    return out
+
+
+def team_csr(labels):
+    """the teams of a label array as (team_off [T+1], members): team t's members are members[team_off[t]:team_off[t+1]],
+    ascending; the teams in ascending order of their labels; a team of fewer than two members is left out (csrc/replan_teams.h
+    builds the same tables for replan_team_kernel)."""
+    groups = {}
+    for i, t in enumerate(labels):
+        if int(t) >= 0:
+            groups.setdefault(int(t), []).append(i)
+    team_off, members = [0], []
+    for t in sorted(groups):
+        if len(groups[t]) >= 2:
+            members.extend(groups[t])
+            team_off.append(len(members))
+    return np.array(team_off, dtype=np.int32), np.array(members, dtype=np.int32)
+
+
+def team_fold(keep, labels):
+    """The step that lets a team share one habitat list: every member's mask becomes the bitwise AND of the masks of all members
+    of its team -- a habitat one of them has visited leaves everybody's list.  keep [n] ints (bit h: habitat h is on the list),
+    labels as team_labels returns them.  Returns the new masks, a list of n ints; AUVs without a teammate keep theirs."""
+    out = [int(k) for k in keep]
+    if len(out) != len(labels):
+        raise ValueError("keep has %d entries, labels %d" % (len(out), len(labels)))
+    team_off, members = team_csr(labels)
+    for t in range(len(team_off) - 1):
+        ms = [int(m) for m in members[team_off[t]:team_off[t + 1]]]
+        k = out[ms[0]]
+        for m in ms[1:]:
+            k &= out[m]
+        for m in ms:
+            out[m] = k
+    return out
+
+
 def first_bucket_commit(course_t, course_xy, t0, max_traj_time, round_span, keep, habitats_xys):
     """One round of replanning's host step (rrt_dubins.py:82-87) on arrays: the points of the course that splitPath
     (:590-602) puts into its first bucket, and removeHabitat (:604-610) applied to the episode's habitat list given as the
@@ -409,8 +464,9 @@ class RRT:
         return [committed[1:], rounds, total]
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
-                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None, commit="host"):
-        """N independent replanning() loops, one exploring launch per round over the AUVs still planning (per-episode
+                         max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None, commit="host",
+                         teams=None):
+        """N replanning() loops -- independent ones unless `teams` is given --, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
         seeds[e]) it equals the call that continues the global stream in that generator's state, and the generator is
@@ -436,9 +492,23 @@ class RRT:
         the courses stay in HBM, one 128-byte record per AUV and round comes back, the host's part of a round is numpy over
         [N] arrays, and the committed trajectories are downloaded once at the end.  The results equal commit="host" (the
         default) in every field.  Seeds only (rngs raises ValueError); the ValueError for a horizon that holds no whole bucket
-        is raised before the round is launched."""
+        is raised before the round is launched.
+
+        teams [N] integers: AUVs with the same label >= 0 form a team that shares one habitat list, a label < 0 is an AUV on
+        its own, labels need not be dense, and a team of one member behaves as no team.  After every round, once all of the
+        round's commits are done, every member's list becomes the intersection of the lists of ALL members of its team
+        (team_fold) -- the members that are not planning any more included, whether they reached the end of their horizon or
+        found no qualifying leaf.  A habitat one AUV has visited so comes off its teammates' lists.  Within a round every
+        member plans against the list it had at the round's start; two teammates may visit the same habitat in one round.
+        Round 1 of every AUV equals the run without teams; round_keep[r] and the rounds dict's habitat list are the team's list
+        at the start of round r; keep / the habitats left of every member are the team's list at the end of the call; costs
+        stay against the original list.  The planner itself is not team-aware (leaf ranking and winner selection are each
+        AUV's own).  Works with rngs (commit="host"), trees_per_auv and shark_of; with commit="device" the fold is
+        replan_team_kernel behind rrt_commit_kernel, and the records that come back carry the team's list.  ValueError, before
+        any launch, for a wrong length, a bool or a value that is no integer."""
         N = len(starts)
         sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
+        labels = None if teams is None else team_labels(teams, N)
         K = int(trees_per_auv)
         if K < 1:
             raise ValueError("trees_per_auv must be >= 1")
@@ -458,7 +528,7 @@ class RRT:
             max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
         if commit == "device":
             return self._replanning_batch_device(starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight,
-                                                 max_iter, seeds, as_arrays, K, sets)
+                                                 max_iter, seeds, as_arrays, K, sets, labels)
         gens = [None] * N     # rngs[e]: the global stream of a sequential call
         streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
         for e in range(N):
@@ -512,6 +582,8 @@ class RRT:
                 keep[e] = new_keep
                 if len(bucket):
                     last[e] = [float(x) for x in bucket[-1]]
+            if labels is not None:  # (once all of the round's commits are done)
+                keep = team_fold(keep, labels)
         done = [e for e in range(N) if traj[e] is not None]
         rows = {e: (np.concatenate(traj[e]) if as_arrays and traj[e] else
                     np.array([[m.x, m.y, m.theta, m.v, m.traj_time_stamp, m.plan_time_stamp, m.length] for m in traj[e]],
@@ -553,9 +625,9 @@ class RRT:
         return costs
 
     def _replanning_batch_device(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter,
-                                 seeds, as_arrays, K, sets):
+                                 seeds, as_arrays, K, sets, labels=None):
         """replanning_batch with commit="device": per round one prepare + run, the winners' selection, and rrt_commit_kernel
-        (Context.replan_commit); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
+        (Context.replan_commit; with team labels replan_team_kernel behind it: the records' keep is the team's); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
         drawing each active AUV's K round seeds from its random.Random."""
         N, H = len(starts), len(all_habitats)
         if seeds is None or len(seeds) != N or any(s is None for s in seeds):
@@ -570,6 +642,8 @@ class RRT:
         ctx = self._ctx
         ctx.set_habitats(hab)  # (the whole list: every episode's own list is its keep mask over this table)
         ctx.replan_begin(last, keep)
+        if labels is not None:
+            ctx.replan_set_teams(labels)
         self._batch = None  # (rerank follows an exploring_batch only)
         log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
         while True:
@@ -605,6 +679,10 @@ class RRT:
             log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won]))
             last[act] = rec["last"]
             keep[act] = rec["keep"]
+        if labels is not None:
+            # a member that stopped planning holds the team's list of its last round: lists only shrink, so the AND over the
+            # host's copies is the team's final one
+            keep = np.array(team_fold(keep, labels), dtype=np.uint64)
         row_off, rows_all = ctx.replan_traj()
         done = [int(e) for e in np.flatnonzero(alive)]
         rows = {e: rows_all[row_off[e]:row_off[e + 1]] for e in done}

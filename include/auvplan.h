@@ -221,13 +221,26 @@ typedef struct {
   int32_t path_len;    /* rows of the winner's course */
   double cost[4];      /* the winner's best_cost (inf without one) */
   double last[7];      /* the AUV's state after the round */
-  uint64_t keep;
+  uint64_t keep;       /* the AUV's list after the round; with teams (auvp_replan_set_teams): its team's list after the round */
   double _reserved[2];
 } auvp_replan_record; /* 128 bytes */
 /* A fleet's state on the handle: last = start7 [n_auvs,7], keep = keep0 [n_auvs] (keep_is_shared != 0: keep0[0] for everyone),
  * an empty log, zeroed counters.  It survives auvp_rrt_prepare*, auvp_rrt_run, auvp_world_set_habitats and
  * auvp_world_set_prob_sets; a new auvp_replan_begin or auvp_destroy drops it. */
 int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, const uint64_t* keep0, int32_t keep_is_shared);
+/* Teams: AUVs of the fleet with the same label team_of[a] >= 0 share one habitat list; a label < 0 is an AUV on its own, labels
+ * need not be dense, and a team of one member is no team.  The rule ("team fold", csrc/replan_teams.h): after every
+ * auvp_replan_commit, once all of the round's commits are done, every member's keep becomes the bitwise AND of the keeps of
+ * ALL members of its team -- those that are not part of the round included.  Within a round every member plans against the
+ * list it had at the round's start.  replan_team_kernel (one wavefront per team) runs behind rrt_commit_kernel on the same
+ * stream and writes the team's list into the state and into the round's records before they are copied back, so nothing more
+ * crosses the bus.  team_of == NULL clears the teams.  Valid after auvp_replan_begin; a new auvp_replan_begin drops the teams.
+ * AUVP_ERR_STATE without a fleet, AUVP_ERR_ARG if n_auvs is not the fleet's size; a call that fails changes nothing. */
+int auvp_replan_set_teams(auvp_handle* h, int32_t n_auvs, const int32_t* team_of /* [n_auvs], NULL: clear */);
+/* Probe: the team fold on the caller's arrays -- the teams' tables built from team_of [n], one launch of replan_team_kernel,
+ * keep_io [n] folded in place.  Needs no world and no fleet; a fleet's state and counters are not touched.  AUVP_ERR_ARG for
+ * n < 1 or a null pointer. */
+int auvp_replan_team_fold(auvp_handle* h, int32_t n, const int32_t* team_of, uint64_t* keep_io);
 /* One round: group g of the last auvp_rrt_group_best is AUV auv_of[g].  One launch (rrt_commit_kernel, one wavefront per
  * group); the round's log space is reserved from the host's copy of the group records before it.  A group without a winner, or
  * whose status is < 0, commits nothing.  out [n_active] may be NULL.  AUVP_ERR_STATE: no auvp_replan_begin, no batch that has
@@ -248,7 +261,8 @@ int auvp_replan_commit_courses(auvp_handle* h, int32_t n_states, const int64_t* 
                                double* rows_out);
 /* Counters since auvp_replan_begin (each pointer may be NULL): the fleet's size (0: none), rounds committed, rows in the log,
  * the bytes the auvp_replan_* entry points have copied to the host, the part of those that auvp_replan_traj copied, and
- * rrt_commit_kernel's time summed over the rounds (HIP events, milliseconds). */
+ * rrt_commit_kernel's time summed over the rounds (HIP events, milliseconds; with teams set the span covers
+ * replan_team_kernel too). */
 int auvp_replan_info(auvp_handle* h, int32_t* n_auvs, int32_t* rounds, int64_t* rows, int64_t* bytes_to_host, int64_t* bytes_traj,
                      double* commit_ms);
 
