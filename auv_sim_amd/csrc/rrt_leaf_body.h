@@ -73,7 +73,9 @@
   // cost[0], cost[1] and the scaled shark term of a leaf, given the ordered or unordered sum `c2num`
   auto total_of = [&](int hits, unsigned long long vis, double ctt, double c2num, double& c0, double& c1, double& c2) {
     c0 = 0.0; c1 = 0.0; c2 = c2num;
-    if (w2_int) c1 = w2 * (double)hits;  // exact: equals `hits` successive rounded additions of an integer weight
+    // exact: equals `hits` successive rounded additions of an integer weight to 0.0 -- whose sum without a hit, or of a weight
+    // of -0.0, is +0.0 and not the product's -0.0: hence the addition to 0.0
+    if (w2_int) c1 = 0.0 + w2 * (double)hits;
     else for (int h = 0; h < hits; h++) c1 = c1 + w2;
     if (ctt > 0) { c1 = c1 / ctt; c2 = c2 / ctt; }
     if (H != 0) c0 = w1 * (double)__popcll(vis) / (double)H;
