@@ -57,7 +57,7 @@ assert GROUP_BEST_DTYPE.itemsize == C.sizeof(RRTGroupBest)
 
 # auvp_replan_record (include/auvplan.h): one AUV's round of the device commit step
 REPLAN_RECORD_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_committed", "<i4"), ("path_len", "<i4"),
-                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("_reserved", "<f8", (2,))])
+                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("claimed", "<u8"), ("_reserved", "<f8")])
 assert REPLAN_RECORD_DTYPE.itemsize == 128
 
 MODES = {"timebin": 0, "plantime": 1, "nn": 2}
@@ -148,6 +148,10 @@ def load():
     if hasattr(L, "auvp_replan_set_teams"):  # (likewise: teams that share one habitat list)
         L.auvp_replan_set_teams.argtypes = [vp, C.c_int32, _ip]
         L.auvp_replan_team_fold.argtypes = [vp, C.c_int32, _ip, C.POINTER(C.c_uint64)]
+    if hasattr(L, "auvp_replan_team_pick"):  # (likewise: the team-aware winner selection)
+        L.auvp_replan_team_pick.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_void_p]
+        L.auvp_replan_team_pick_courses.argtypes = [vp, C.c_int32, _ip, _u64p, C.c_int32, _ip, C.c_int32, _i64p, _dp, _dp, _dp, _dp,
+                                                    _ip, _ip, _dp, C.c_void_p, _u64p]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -607,6 +611,43 @@ class Context:
         self._chk(self.L.auvp_replan_team_fold(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(C.POINTER(C.c_uint64))))
         return kp
 
+    def replan_team_pick(self, auv_of, K):
+        """the team-aware winner selection in place of rrt_group_best (auvp_replan_team_pick): group g of the batch that just
+        ran = episodes g*K .. g*K+K-1 = AUV auv_of[g].  Returns [n_active] GROUP_BEST_DTYPE records: rrt_group_best's for AUVs
+        without a teammate, the winner under the teammates' claims and its score for the members of teams."""
+        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
+        self._chk(self.L.auvp_replan_team_pick(self.h, len(a), _p(a, _ip), int(K), out.ctypes.data_as(C.c_void_p)))
+        return out[:len(a)]
+
+    def replan_team_pick_courses(self, team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights):
+        """probe: rrt_group_best_kernel, rrt_course_words_kernel and replan_team_pick_kernel on the caller's candidates against
+        the world's habitat table and time bins.  courses_xyt: n_active * K arrays [L,3] (L == 0: a tree without a leaf), in
+        group order; cost4 [E,4], leaf_t [E], length [E], bin_lo / bin_hi [E].  Returns (records [n_active], claimed [n_active])."""
+        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
+        kp = np.array(keep, dtype=np.uint64).reshape(-1)
+        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        E = len(a) * int(K)
+        if len(kp) != len(t) or len(courses_xyt) != E:
+            raise ValueError("team_of / keep, or auv_of x K / courses, do not match")
+        off = np.zeros(E + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(c) for c in courses_xyt])
+        flat = _f64(np.concatenate([_f64(c, (-1, 3)) for c in courses_xyt]) if E else [], (-1, 3))
+        if len(flat) == 0:
+            flat = np.zeros((1, 3))
+        c4, lt, ln = _f64(cost4, (E, 4)), _f64(leaf_t, (E,)), _f64(length, (E,))
+        lo = np.ascontiguousarray(np.asarray(bin_lo, dtype=np.int32).reshape(E))
+        hi = np.ascontiguousarray(np.asarray(bin_hi, dtype=np.int32).reshape(E))
+        w = _f64(weights, (3,))
+        out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
+        claimed = np.zeros(max(len(a), 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._chk(self.L.auvp_replan_team_pick_courses(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(u64p), len(a), _p(a, _ip), int(K),
+                                                       off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(c4), _p(lt), _p(ln),
+                                                       _p(lo, _ip), _p(hi, _ip), _p(w), out.ctypes.data_as(C.c_void_p),
+                                                       claimed.ctypes.data_as(u64p)))
+        return out[:len(a)], claimed[:len(a)]
+
     def replan_commit(self, auv_of, round_span, records=True):
         """one round behind rrt_group_best: group g is AUV auv_of[g]; the winners' first buckets go into the log, the states
         are updated in HBM.  Returns [n_active] REPLAN_RECORD_DTYPE records (None with records=False)."""
@@ -645,7 +686,8 @@ class Context:
 
     def replan_info(self):
         """counters since replan_begin: n_auvs, rounds, rows, bytes_to_host (what the replan entry points copied to the host),
-        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, with teams replan_team_kernel's too, summed)"""
+        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, with teams replan_team_kernel's too, and with replan_team_pick
+        rrt_course_words_kernel's and replan_team_pick_kernel's, summed)"""
         a, r = C.c_int32(0), C.c_int32(0)
         rows, b, bt, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         self._chk(self.L.auvp_replan_info(self.h, C.byref(a), C.byref(r), C.byref(rows), C.byref(b), C.byref(bt), C.byref(ms)))

@@ -1,7 +1,8 @@
 // replan_host.h -- host side of the device commit step of RRT.replanning_batch (auvp_replan_*, include/auvplan.h): the fleet's
 // state on the handle (last [n,7], keep [n], the trajectory log, the teams), the launch of rrt_commit_kernel (replan_kernels.hip)
 // behind auvp_rrt_group_best and of replan_team_kernel behind it where the fleet has teams, the one download at the end, and the
-// probe entries that run the kernels' rules on the caller's courses and masks.
+// probe entries that run the kernels' rules on the caller's courses and masks; and the team-aware winner selection
+// (auvp_replan_team_pick: rrt_group_best_kernel, rrt_course_words_kernel, replan_team_pick_kernel -- replan_pick.h).
 // Every index the kernel uses is computed here from host data: the group records' host copy (h->group_best) sizes the course
 // scratch and the round's log space before the launch.
 // Included at the end of auvplan.hip.
@@ -9,12 +10,18 @@
 #define AUVP_REPLAN_HOST_H
 #include "replan_commit.h"
 #include "replan_teams.h"
+#include "replan_pick.h"
 
+extern "C" hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A, hipStream_t stream);
+extern "C" hipError_t auvpi_replan_pick_launch(const auvp::ReplanPickDev* T, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_team_launch(const auvp::ReplanTeamDev* T, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_commit_launch(const auvp::RrtBuffers* B, const auvp::ReplanCommitDev* A, int n_episodes, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_gather_launch(const auvp::ReplanSegment* seg, int n_seg, const double* log, double* out, hipStream_t stream);
 
 static_assert(sizeof(auvp_replan_record) == sizeof(auvp::ReplanRecord), "round record layout");
+// the public record's `claimed` is the first of the internal record's two reserved doubles
+static_assert(offsetof(auvp_replan_record, claimed) == offsetof(auvp::ReplanRecord, _reserved), "round record layout: claimed");
+static_assert(offsetof(auvp_replan_record, keep) == offsetof(auvp::ReplanRecord, keep), "round record layout: keep");
 
 namespace {
 
@@ -29,10 +36,17 @@ struct ReplanState {
   std::vector<Piece> pieces;               // in round order
   std::vector<auvp::ReplanRecord> rec_host;
   long long bytes_to_host = 0, bytes_traj = 0;
-  double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's), summed over the rounds
+  double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's; with auvp_replan_team_pick: and
+                                           // its two kernels'), summed over the rounds
   // the fleet's teams (auvp_replan_set_teams): the CSR of replan_teams.h in HBM; n_teams == 0: none, nothing more is launched
   int n_teams = 0;
   DevBuf team_off, team_members, slot_of;
+  // the team-aware selection (auvp_replan_team_pick) of the round being committed: the masks the members saw, [pick_best.size()]
+  // in HBM, and the group records it left -- the commit copies the masks into its records only if the handle's group records
+  // are still those
+  DevBuf words, leaf_t, claimed, pick_auv, pick_slot_of;
+  std::vector<RrtGroupBest> pick_best;
+  bool pick_pending = false;
 };
 
 ReplanState* replan_of(auvp_handle* h) {
@@ -83,6 +97,14 @@ int replan_launch(auvp_handle* h, ReplanState& S, const auvp::RrtBuffers* B, auv
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, auvpi_replan_commit_launch(B, &A, h->E, h->stream));
   if (teams) HIPCHK(h, auvpi_replan_team_launch(&T, h->stream));
+  if (B && S.pick_pending) {
+    // the masks of auvp_replan_team_pick into the records' `claimed`, device to device, if the group records are still its
+    S.pick_pending = false;
+    if (S.pick_best.size() == slots.size() && h->group_best.size() == slots.size() &&
+        memcmp(S.pick_best.data(), h->group_best.data(), slots.size() * sizeof(RrtGroupBest)) == 0)
+      HIPCHK(h, hipMemcpy2DAsync(reinterpret_cast<char*>(S.rec.p) + offsetof(auvp::ReplanRecord, _reserved), sizeof(auvp::ReplanRecord), S.claimed.p,
+                                 sizeof(uint64_t), sizeof(uint64_t), slots.size(), hipMemcpyDeviceToDevice, h->stream));
+  }
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   S.rec_host.resize(slots.size());
   HIPCHK(h, hipMemcpyAsync(S.rec_host.data(), S.rec.p, slots.size() * sizeof(auvp::ReplanRecord), hipMemcpyDeviceToHost, h->stream));
@@ -117,6 +139,7 @@ int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, cons
   S.bytes_to_host = S.bytes_traj = 0;
   S.commit_ms = 0.0;
   S.n_teams = 0;  // (the teams were the old fleet's)
+  S.pick_pending = false;
   S.n_auvs = n_auvs;
   return AUVP_OK;
 }
@@ -223,6 +246,169 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
   S.commit_ms += ms;
   h->last_ms = ms; h->last_grid = G; h->last_block = 64; h->last_lds = 0;
   if (out) memcpy(out, S.rec_host.data(), (size_t)G * sizeof(auvp::ReplanRecord));
+  return AUVP_OK;
+}
+
+int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, struct auvp_rrt_group_best* out) {
+  if (!h) return AUVP_ERR_ARG;
+  ReplanState* Sp = static_cast<ReplanState*>(h->replan);
+  if (!Sp || Sp->n_auvs < 1) return fail(h, AUVP_ERR_STATE, "auvp_replan_begin not called");
+  ReplanState& S = *Sp;
+  if (S.n_teams < 1) return fail(h, AUVP_ERR_STATE, "the fleet has no teams (auvp_replan_set_teams)");
+  if (!h->have_batch) return fail(h, AUVP_ERR_STATE, "no batch has run");
+  if (n_active < 1 || K < 1 || !auv_of) return fail(h, AUVP_ERR_ARG, "need n_active >= 1, K >= 1 and auv_of");
+  const int E = h->E;
+  if ((long long)n_active * K != (long long)E) return fail(h, AUVP_ERR_ARG, "the batch has %d episodes, not %d x %d", E, n_active, K);
+  const int G = n_active;
+  std::vector<int32_t> slot_of((size_t)S.n_auvs, -1);
+  for (int g = 0; g < G; g++) {
+    const int a = auv_of[g];
+    if (a < 0 || a >= S.n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, S.n_auvs);
+    if (slot_of[(size_t)a] >= 0) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
+    slot_of[(size_t)a] = (int32_t)g;
+  }
+  std::vector<int32_t> group_off((size_t)G + 1);
+  for (int g = 0; g <= G; g++) group_off[(size_t)g] = (int32_t)(g * K);
+  HIPCHK(h, hipSetDevice(h->device));
+  // a course has at most one element per node and per path point of its tree: the scratch is sized from the batch's capacities
+  // (the summaries stay in HBM), the same place for every episode
+  const int64_t stride = (int64_t)h->B.cap_nodes + (int64_t)h->B.cap_points;
+  HIPCHK(h, S.words.reserve((size_t)E * (size_t)stride * sizeof(uint64_t)));
+  HIPCHK(h, S.leaf_t.reserve((size_t)E * sizeof(double)));
+  HIPCHK(h, S.claimed.reserve((size_t)G * sizeof(uint64_t)));
+  h->have_group = false;
+  S.pick_pending = false;
+  int rc;
+  if ((rc = upload(h, h->d_group_off, group_off.data(), group_off.size()))) return rc;
+  if ((rc = upload(h, S.pick_auv, auv_of, (size_t)G))) return rc;
+  if ((rc = upload(h, S.pick_slot_of, slot_of.data(), slot_of.size()))) return rc;
+  HIPCHK(h, h->d_group_best.reserve((size_t)G * sizeof(RrtGroupBest)));
+  HIPCHK(h, hipMemsetAsync(S.claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
+  auvp::ReplanWordsDev A{};
+  A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
+  A.stride = stride;
+  A.auv_of = S.pick_auv.as<int32_t>(); A.last = S.last.as<double>();
+  A.hab = h->W.hab; A.hab_t = h->W.hab_t; A.bins = h->W.bins;
+  A.words = S.words.as<uint64_t>(); A.leaf_t = S.leaf_t.as<double>();
+  auvp::ReplanPickDev T{};
+  T.n_teams = S.n_teams; T.K = K; T.n_slots = G;
+  T.team_off = S.team_off.as<int32_t>(); T.members = S.team_members.as<int32_t>(); T.slot_of = S.pick_slot_of.as<int32_t>();
+  T.keep = S.keep.as<uint64_t>();
+  T.summary = h->B.summary;
+  T.words = A.words; T.stride = stride; T.leaf_t = A.leaf_t;
+  T.best = h->d_group_best.as<RrtGroupBest>(); T.claimed = S.claimed.as<uint64_t>();
+  T.w1 = h->P.w[0]; T.w2 = h->P.w[1];
+  // every group gets rrt_group_best_kernel's record; the pick rewrites those of the members of teams of two or more
+  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
+                     h->B.summary, h->d_group_off.as<int32_t>(), h->d_group_best.as<RrtGroupBest>(), G);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, auvpi_replan_words_launch(&h->B, &A, h->stream));
+  HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  h->group_best.resize((size_t)G);
+  HIPCHK(h, hipMemcpyAsync(h->group_best.data(), h->d_group_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  S.commit_ms += ms;
+  h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
+  S.pick_best = h->group_best;
+  S.pick_pending = true;
+  h->have_group = true;
+  if (out) memcpy(out, h->group_best.data(), (size_t)G * sizeof(RrtGroupBest));
+  return AUVP_OK;
+}
+
+int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                  const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
+                                  const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
+                                  const int32_t* bin_hi, const double* weights3, struct auvp_rrt_group_best* out, uint64_t* claimed_out) {
+  if (!h) return AUVP_ERR_ARG;
+  if (n_auvs < 1 || n_active < 1 || K < 1 || !team_of || !keep || !auv_of || !course_off || !cost4 || !leaf_t || !bin_lo || !bin_hi ||
+      !weights3 || !out || !claimed_out)
+    return fail(h, AUVP_ERR_ARG, "bad probe arguments");
+  if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
+  if ((long long)n_active * K > 0x7fffffffll) return fail(h, AUVP_ERR_ARG, "too many candidates");
+  const int G = n_active, E = n_active * K;
+  std::vector<int32_t> slot_of((size_t)n_auvs, -1);
+  for (int g = 0; g < G; g++) {
+    const int a = auv_of[g];
+    if (a < 0 || a >= n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, n_auvs);
+    if (slot_of[(size_t)a] >= 0) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
+    slot_of[(size_t)a] = (int32_t)g;
+  }
+  if (course_off[0] != 0) return fail(h, AUVP_ERR_ARG, "course_off[0] != 0");
+  for (int e = 0; e < E; e++)
+    if (course_off[e + 1] < course_off[e] || course_off[e + 1] - course_off[e] > 0x7fffffffll)
+      return fail(h, AUVP_ERR_ARG, "course_off is not an ascending list of row offsets");
+  const long long total = course_off[E];
+  if (total > 0 && !courses_xyt) return fail(h, AUVP_ERR_ARG, "courses_xyt is null");
+  for (int e = 0; e < E; e++)
+    if (bin_lo[e] < 0 || bin_hi[e] > h->W.n_bins) return fail(h, AUVP_ERR_ARG, "candidate %d: bins %d .. %d outside the table of %d", e, bin_lo[e], bin_hi[e], h->W.n_bins);
+  // the candidates as summaries: what the two selection kernels read of one
+  std::vector<RrtSummary> summ((size_t)E);
+  std::vector<int32_t> len((size_t)E), group_off((size_t)G + 1);
+  memset(summ.data(), 0, summ.size() * sizeof(RrtSummary));
+  for (int e = 0; e < E; e++) {
+    const int L = (int)(course_off[e + 1] - course_off[e]);
+    len[(size_t)e] = L;
+    RrtSummary& s = summ[(size_t)e];
+    s.best_leaf = L > 0 ? 0 : -1;
+    s.best_path_len = L;
+    for (int k = 0; k < 4; k++) s.best_cost[k] = cost4[4 * (size_t)e + k];
+    s.best_length = length ? length[e] : 0.0;
+  }
+  for (int g = 0; g <= G; g++) group_off[(size_t)g] = (int32_t)(g * K);
+  const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
+  HIPCHK(h, hipSetDevice(h->device));
+  // the probe's own buffers: the fleet's state, the handle's group records and the counters stay as they are
+  DevBuf d_summ, d_len, d_goff, d_off, d_xyt, d_lt, d_lo, d_hi, d_keep, d_slot, d_toff, d_tmem, d_words, d_best, d_claimed;
+  int rc;
+  if ((rc = upload(h, d_summ, summ.data(), summ.size()))) return rc;
+  if ((rc = upload(h, d_len, len.data(), len.size()))) return rc;
+  if ((rc = upload(h, d_goff, group_off.data(), group_off.size()))) return rc;
+  if ((rc = upload(h, d_off, course_off, (size_t)E + 1))) return rc;
+  if ((rc = upload(h, d_xyt, courses_xyt, (size_t)total * 3))) return rc;
+  if ((rc = upload(h, d_lt, leaf_t, (size_t)E))) return rc;
+  if ((rc = upload(h, d_lo, bin_lo, (size_t)E))) return rc;
+  if ((rc = upload(h, d_hi, bin_hi, (size_t)E))) return rc;
+  if ((rc = upload(h, d_keep, keep, (size_t)n_auvs))) return rc;
+  if ((rc = upload(h, d_slot, slot_of.data(), slot_of.size()))) return rc;
+  if ((rc = upload(h, d_toff, csr.team_off.data(), csr.team_off.size()))) return rc;
+  if ((rc = upload(h, d_tmem, csr.members.data(), csr.members.size()))) return rc;
+  HIPCHK(h, d_words.reserve((size_t)std::max<long long>(total, 1) * sizeof(uint64_t)));
+  HIPCHK(h, d_best.reserve((size_t)G * sizeof(RrtGroupBest)));
+  HIPCHK(h, d_claimed.reserve((size_t)G * sizeof(uint64_t)));
+  HIPCHK(h, hipMemsetAsync(d_claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
+  auvp::ReplanWordsDev A{};
+  A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
+  A.from_courses = 1;
+  A.off = d_off.as<int64_t>(); A.xyt = d_xyt.as<double>(); A.len = d_len.as<int32_t>();
+  A.bin_lo = d_lo.as<int32_t>(); A.bin_hi = d_hi.as<int32_t>();
+  A.hab = h->W.hab; A.hab_t = h->W.hab_t; A.bins = h->W.bins;
+  A.words = d_words.as<uint64_t>();
+  auvp::ReplanPickDev T{};
+  T.n_teams = csr.n_teams(); T.K = K; T.n_slots = G;
+  T.team_off = d_toff.as<int32_t>(); T.members = d_tmem.as<int32_t>(); T.slot_of = d_slot.as<int32_t>();
+  T.keep = d_keep.as<uint64_t>();
+  T.summary = d_summ.as<RrtSummary>();
+  T.words = A.words; T.off = A.off; T.leaf_t = d_lt.as<double>();
+  T.best = d_best.as<RrtGroupBest>(); T.claimed = d_claimed.as<uint64_t>();
+  T.w1 = weights3[0]; T.w2 = weights3[1];
+  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
+                     d_summ.as<RrtSummary>(), d_goff.as<int32_t>(), d_best.as<RrtGroupBest>(), G);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, auvpi_replan_words_launch(nullptr, &A, h->stream));
+  HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out, d_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(claimed_out, d_claimed.p, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
   return AUVP_OK;
 }
 

@@ -7,6 +7,7 @@
 //   replan_gather_kernel  the log's pieces into AUV order, for the one download at the end
 //   replan_team_kernel  one wavefront per team (replan_teams.h): every member's keep becomes the AND of the members' masks,
 //                       in the state array and in the round's records
+//   rrt_course_words_kernel, replan_team_pick_kernel  the team-aware winner selection (replan_pick.h), see below
 //
 // Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
 #include <hip/hip_runtime.h>
@@ -17,6 +18,8 @@
 #include "rrt_group_kernel.h"
 #include "replan_commit.h"
 #include "replan_teams.h"
+#include "replan_pick.h"
+#include "rrt_course_walk.h"
 
 namespace auvp {
 
@@ -165,7 +168,134 @@ static __global__ __launch_bounds__(REPLAN_TEAM_WAVES * 64) void replan_team_ker
   }
 }
 
+// ---- team_pick="claims" (replan_pick.h) ----------------------------------------------------------------------------------------
+//
+// rrt_course_words_kernel: one wavefront (= one workgroup) per episode that has a leaf; one 64-bit word per point of its best
+// course into a scratch buffer in HBM: the containment mask of a counted point, 0 for a point in no selected bin.  Row 0 is the
+// AUV's committed state, as in the commit rule.  This is the parallel part of the selection: E * L * H distance tests with
+// nothing dependent between them.  LANES OVER POINTS, the habitat table in LDS: the walk of the course already has a point per
+// lane (a node's path points are spread over the lanes, as in rrt_final_course), so each lane tests its own point against the
+// H table rows, which all lanes read at one LDS address (a broadcast, no bank conflict).  64 points cost H steps and no
+// cross-lane operation; one lane per habitat against a broadcast point would cost 64 ballots for the same 64 points (more
+// steps whenever H < 64 -- fleets here have about ten habitats) and a shuffle per point on top.
+static __global__ __launch_bounds__(64) void rrt_course_words_kernel(RrtBuffers B, ReplanWordsDev A) {
+  __shared__ double s_hab[REPLAN_MAX_HAB * 3], s_habt[REPLAN_MAX_HAB];
+  const int ep = blockIdx.x;
+  if (ep >= A.n_episodes) return;  // (the whole workgroup)
+  const int lane = lane_id();
+  const int H = A.H < REPLAN_MAX_HAB ? (A.H > 0 ? A.H : 0) : REPLAN_MAX_HAB;
+  for (int i = lane; i < 3 * H; i += 64) s_hab[i] = A.hab[i];
+  for (int i = lane; i < H; i += 64) s_habt[i] = A.hab_t[i];
+  __syncthreads();
+  int lo = A.bin_lo ? A.bin_lo[ep] : 0, hi = A.bin_hi ? A.bin_hi[ep] : A.n_bins;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > A.n_bins ? A.n_bins : hi;
+  uint64_t* w = A.words + (A.off ? A.off[ep] : (int64_t)ep * A.stride);
+  const double* bins = A.bins;
+  if (A.from_courses) {  // the probe: the caller's course
+    const int L = A.len[ep];
+    const double* c = A.xyt + 3 * (size_t)A.off[ep];
+    for (int i = lane; i < L; i += 64) w[i] = replan_pick_word(s_hab, s_habt, H, bins, lo, hi, c[3 * (size_t)i], c[3 * (size_t)i + 1], c[3 * (size_t)i + 2]);
+    return;
+  }
+  const RrtSummary* s = B.summary + ep;
+  const int L = s->best_path_len;
+  if (s->best_leaf < 0 || L < 1 || (int64_t)L > A.stride) return;  // (a course longer than the host's bound: no words, and no candidate)
+  const double* last = A.last + (size_t)REPLAN_ROW * (size_t)A.auv_of[ep / A.K];
+  double* leaf_t = A.leaf_t + ep;
+  rrt_course_walk_xyt(B, ep, [&](int at, double x, double y, double t) {
+    if (at < 0 || at >= L) return;
+    if (at == 0) { x = last[0]; y = last[1]; t = last[4]; }
+    w[at] = replan_pick_word(s_hab, s_habt, H, bins, lo, hi, x, y, t);
+    if (at == L - 1) *leaf_t = t;
+  });
+}
+
+// wave-wide OR of a 64-bit word, as wave_and_u64
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) {
+  int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+  lo |= __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xf, 0xf, false); hi |= __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xf, 0xf, false);
+  lo |= __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xf, 0xf, false); hi |= __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xf, 0xf, false);
+  lo |= __builtin_amdgcn_update_dpp(0, lo, 0x122, 0xf, 0xf, false); hi |= __builtin_amdgcn_update_dpp(0, hi, 0x122, 0xf, 0xf, false);
+  lo |= __builtin_amdgcn_update_dpp(0, lo, 0x121, 0xf, 0xf, false); hi |= __builtin_amdgcn_update_dpp(0, hi, 0x121, 0xf, 0xf, false);
+  const int l = __builtin_amdgcn_readlane(lo, 0) | __builtin_amdgcn_readlane(lo, 16) | __builtin_amdgcn_readlane(lo, 32) |
+                __builtin_amdgcn_readlane(lo, 48);
+  const int h = __builtin_amdgcn_readlane(hi, 0) | __builtin_amdgcn_readlane(hi, 16) | __builtin_amdgcn_readlane(hi, 32) |
+                __builtin_amdgcn_readlane(hi, 48);
+  return ((uint64_t)(uint32_t)h << 32) | (uint32_t)l;
+}
+
+// replan_team_pick_kernel: one wavefront per team of the CSR.  The members run serially -- the rule's own dependence: a member
+// is judged by what the members before it claimed.  Per candidate the lanes stride over its words (replan_pick_hits), one wave
+// reduction follows (an integer sum and a 64-bit OR), and every lane computes the score and the fold on the same numbers.  Runs
+// behind rrt_group_best_kernel and rrt_course_words_kernel on the same stream: it rewrites winner, path_len, cost and length of
+// the members' group records (status: a failed member's stays; n_with_leaf stays) and leaves every other group's record alone.
+// Teams are disjoint: plain stores.
+static __global__ __launch_bounds__(REPLAN_PICK_WAVES * 64) void replan_team_pick_kernel(ReplanPickDev T) {
+  const int t = (int)blockIdx.x * REPLAN_PICK_WAVES + (int)(threadIdx.x >> 6);
+  if (t >= T.n_teams) return;  // (the whole wavefront)
+  const int lane = lane_id();
+  const int lo = T.team_off[t], hi = T.team_off[t + 1];
+  const double inf = __builtin_inf();
+  uint64_t claimed = 0;
+  for (int i = lo; i < hi; i++) {
+    const int m = T.members[i];
+    const int g = T.slot_of[m];
+    if (g < 0 || g >= T.n_slots) continue;  // (not planning in this round; the same on every lane)
+    const uint64_t mask = T.keep[m] & ~claimed;
+    ReplanPickBest b{inf, -1};
+    double cost[4] = {inf, inf, inf, inf};
+    uint64_t vis_w = 0;
+    for (int k = 0; k < T.K; k++) {
+      const int ep = g * T.K + k;
+      const RrtSummary* s = T.summary + ep;
+      const int L = s->best_path_len;
+      if (s->best_leaf < 0 || L < 1 || (!T.off && (int64_t)L > T.stride)) continue;  // (the same on every lane)
+      const uint64_t* w = T.words + (T.off ? T.off[ep] : (int64_t)ep * T.stride);
+      const ReplanPickHits hv = replan_pick_hits(w, lane, L, 64, mask);
+      const int hits = wave_sum_i32(hv.hits);
+      const uint64_t vis = wave_or_u64(hv.vis);
+      double sc[4];
+      replan_pick_score(hits, vis, mask, T.w1, T.w2, s->best_cost[3], T.leaf_t[ep], sc);
+      if (replan_pick_fold(b, sc[0], k)) {
+        cost[0] = sc[0]; cost[1] = sc[1]; cost[2] = sc[2]; cost[3] = sc[3];
+        vis_w = vis;
+      }
+    }
+    if (lane == 0) {
+      RrtGroupBest r = T.best[g];
+      if (r.status >= 0) r.status = b.k >= 0 ? 0 : 1 /* AUVP_NO_QUALIFYING_LEAF */;
+      r.winner = b.k >= 0 ? g * T.K + b.k : -1;
+      r.path_len = 0;
+      r.length = 0.0;
+      if (b.k >= 0) {
+        const RrtSummary* s = T.summary + (g * T.K + b.k);
+        r.path_len = s->best_path_len;
+        r.length = s->best_length;
+      }
+      r.cost[0] = cost[0]; r.cost[1] = cost[1]; r.cost[2] = cost[2]; r.cost[3] = cost[3];
+      T.best[g] = r;
+      T.claimed[g] = claimed;
+    }
+    claimed |= vis_w;
+  }
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A,
+                                                                                      hipStream_t stream) {
+  if (A->n_episodes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(auvp::rrt_course_words_kernel, dim3(A->n_episodes), dim3(64), 0, stream, B ? *B : auvp::RrtBuffers{}, *A);
+  return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_pick_launch(const auvp::ReplanPickDev* T, hipStream_t stream) {
+  if (T->n_teams <= 0) return hipSuccess;
+  const int blocks = (T->n_teams + auvp::REPLAN_PICK_WAVES - 1) / auvp::REPLAN_PICK_WAVES;
+  hipLaunchKernelGGL(auvp::replan_team_pick_kernel, dim3(blocks), dim3(auvp::REPLAN_PICK_WAVES * 64), 0, stream, *T);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_team_launch(const auvp::ReplanTeamDev* T, hipStream_t stream) {
   if (T->n_teams <= 0) return hipSuccess;

@@ -188,6 +188,98 @@ def team_fold(keep, labels):
     return out
 
 
+def course_habitat_words(course_xy, course_t, bins, bin_lo, bin_hi, habitats_xys):
+    """One Python int per course point: bit h is set iff habitat h of habitats_xys [H,3] contains the point
+    (math.sqrt(dx * dx + dy * dy) <= size, first_bucket_commit's test), and 0 for a point whose time stamp lies in none of the
+    shark bins bins[bin_lo:bin_hi] -- habitat_shark_cost_func (cost.py:171-179) skips such a point entirely.  The words do not
+    depend on any habitat list: rescore judges them under a mask.  csrc/replan_pick.h: replan_pick_word."""
+    xy = np.asarray(course_xy, dtype=np.float64).reshape(-1, 2)
+    t = np.asarray(course_t, dtype=np.float64).reshape(-1)
+    n = len(xy)
+    b = np.asarray(bins, dtype=np.float64).reshape(-1, 2)[max(int(bin_lo), 0):max(int(bin_hi), 0)]
+    hb = np.asarray(habitats_xys, dtype=np.float64).reshape(-1, 3)
+    if n == 0 or len(b) == 0 or len(hb) == 0:
+        return [0] * n
+    counted = ((t[:, None] >= b[None, :, 0]) & (t[:, None] <= b[None, :, 1])).any(axis=1)
+    dx, dy = xy[:, None, 0] - hb[None, :, 0], xy[:, None, 1] - hb[None, :, 1]
+    with np.errstate(over="ignore", invalid="ignore"):
+        inside = np.sqrt(dx * dx + dy * dy) <= hb[None, :, 2]
+    bits = inside.astype(object) @ np.array([1 << h for h in range(len(hb))], dtype=object)
+    return [int(w) if c else 0 for w, c in zip(bits, counted)]
+
+
+def rescore(words, mask, c2, leaf_time, weights):
+    """The cost exploring would have given a course against the habitat list `mask` (bit h: habitat h is on it), from the
+    course's words (course_habitat_words), its shark term c2 as the summary reports it (already divided by the leaf time; it
+    does not depend on the list) and its leaf's traj_time_stamp: habitat_shark_cost_func's habitat terms, float operation by
+    float operation as the leaf pass computes them (csrc/rrt_leaf_body.h: total_of).  A counted point hits the lowest-numbered
+    habitat of mask that contains it.  Returns ([total, c0, c1, c2], vis) with vis the set of habitats hit.
+    csrc/replan_pick.h: replan_pick_hits + replan_pick_score."""
+    mask = int(mask)
+    hits, vis = 0, 0
+    for w in words:
+        m = int(w) & mask
+        if m:
+            hits += 1
+            vis |= m & -m
+    n_list = bin(mask).count("1")
+    w1, w2, c2, leaf_time = float(weights[0]), float(weights[1]), float(c2), float(leaf_time)
+    c0, c1 = 0.0, 0.0
+    if w2 == w2 and abs(w2) < 1048576.0 and w2 == float(round(w2)):
+        c1 = 0.0 + w2 * float(hits)  # (an integer weight: exactly `hits` rounded additions; 0.0 + ...: never -0.0)
+    else:
+        for _ in range(hits):
+            c1 = c1 + w2
+    if leaf_time > 0:
+        c1 = c1 / leaf_time
+    if n_list != 0:
+        c0 = w1 * float(bin(vis).count("1")) / float(n_list)
+    return [((0.0 + c0) + c1) + c2, c0, c1, c2], vis
+
+
+def team_pick_claims(labels, keep, active, cands, weights):
+    """The team-aware winner selection of replanning_batch(team_pick="claims") for one round -- the definition the device
+    kernels (csrc/replan_pick.h, replan_kernels.hip) match bit for bit.  labels [n] as team_labels returns them, keep [n] the
+    lists at the round's start, active: the AUVs that plan in this round (group g is AUV active[g]); cands[g]: that AUV's K
+    candidates in tree order, each None (the tree has no leaf) or a dict(words=course_habitat_words of the tree's own best
+    course, cost=its four costs as the leaf pass ranked it under keep, leaf_time=its leaf's time).
+
+    Every team of two or more: claimed = 0; its members that are in `active`, in ascending AUV index: each candidate is scored
+    by rescore under keep[m] & ~claimed (c2 = cost[3]); the winner is rrt_group_best's fold over the scores -- score < best so
+    far, from inf: the lowest tree among equal scores, never a NaN, never a tree without a leaf --; claimed |= the winner's vis
+    (its whole course).  A member without a winner claims nothing.  Everybody else gets the same fold over cost[0].
+    Returns per group a dict(winner=tree or -1, cost=[4] the winner's score (inf without one), claimed=the mask the member
+    saw (0 without teammates), n_with_leaf)."""
+    active = [int(a) for a in active]
+    slot_of = {a: g for g, a in enumerate(active)}
+    inf = float("inf")
+    out = []
+    for g in range(len(active)):  # rrt_group_best_kernel's record
+        best, win, cost = inf, -1, [inf] * 4
+        for k, c in enumerate(cands[g]):
+            if c is not None and float(c["cost"][0]) < best:
+                best, win, cost = float(c["cost"][0]), k, [float(x) for x in c["cost"]]
+        out.append(dict(winner=win, cost=cost, claimed=0, n_with_leaf=sum(c is not None for c in cands[g])))
+    team_off, members = team_csr(labels)
+    for t in range(len(team_off) - 1):
+        claimed = 0
+        for m in members[team_off[t]:team_off[t + 1]]:
+            g = slot_of.get(int(m))
+            if g is None:
+                continue
+            mask = int(keep[int(m)]) & ~claimed
+            best, win, cost, vis_w = inf, -1, [inf] * 4, 0
+            for k, c in enumerate(cands[g]):
+                if c is None:
+                    continue
+                s, vis = rescore(c["words"], mask, c["cost"][3], c["leaf_time"], weights)
+                if s[0] < best:
+                    best, win, cost, vis_w = s[0], k, s, vis
+            out[g].update(winner=win, cost=cost, claimed=claimed)
+            claimed |= vis_w
+    return out
+
+
 def first_bucket_commit(course_t, course_xy, t0, max_traj_time, round_span, keep, habitats_xys):
     """One round of replanning's host step (rrt_dubins.py:82-87) on arrays: the points of the course that splitPath
     (:590-602) puts into its first bucket, and removeHabitat (:604-610) applied to the episode's habitat list given as the
@@ -465,7 +557,7 @@ class RRT:
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
                          max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None, commit="host",
-                         teams=None):
+                         teams=None, team_pick=None):
         """N replanning() loops -- independent ones unless `teams` is given --, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
@@ -502,13 +594,39 @@ class RRT:
         member plans against the list it had at the round's start; two teammates may visit the same habitat in one round.
         Round 1 of every AUV equals the run without teams; round_keep[r] and the rounds dict's habitat list are the team's list
         at the start of round r; keep / the habitats left of every member are the team's list at the end of the call; costs
-        stay against the original list.  The planner itself is not team-aware (leaf ranking and winner selection are each
-        AUV's own).  Works with rngs (commit="host"), trees_per_auv and shark_of; with commit="device" the fold is
+        stay against the original list.  Without team_pick (below) the planner itself is not team-aware (leaf ranking and winner
+        selection are each AUV's own).  Works with rngs (commit="host"), trees_per_auv and shark_of; with commit="device" the fold is
         replan_team_kernel behind rrt_commit_kernel, and the records that come back carry the team's list.  ValueError, before
-        any launch, for a wrong length, a bool or a value that is no integer."""
+        any launch, for a wrong length, a bool or a value that is no integer.
+
+        team_pick="claims" (needs teams; None: the call as described so far) makes the winner selection team-aware, so that the K
+        trees of trees_per_auv spread a team out instead of steering two members to one habitat.  Per round and team of two or
+        more, claimed = 0 and the members that plan in this round are taken in ascending AUV index: each of the member's K
+        trees offers its own best course (as the leaf pass ranked it under the member's list), every such course is scored
+        again under list & ~claimed -- the cost exploring would have given it against the shorter list: only the habitat terms
+        change, the shark term does not --, the winner is the usual fold over these scores, and the habitats its WHOLE course
+        visits under that mask join claimed (team_pick_claims is the definition).  The first planning member of a team sees
+        claimed == 0: its scores are the trees' own costs bit for bit and its winner is the one without team_pick; so are those of
+        AUVs without a teammate.  The commit and the team fold run unchanged on the chosen winners (under the member's own list:
+        a habitat visited is visited).  round_tree names the chosen tree; round_cost is the winner's score UNDER THE MASK IT WAS
+        JUDGED BY, not its cost under the member's list; with as_arrays=True round_claimed [R] (uint64) is the claimed mask the
+        member saw.  Not done: ranking a tree's leaves again under the reduced list (one leaf pass per member, one after the
+        other) -- a tree's candidate is always its best leaf under the member's own list.  Works with trees_per_auv (any K),
+        shark_of, seeds and both commit routes; with commit="host" every candidate's course is copied to the host, with
+        commit="device" rrt_course_words_kernel and replan_team_pick_kernel run behind the leaf pass and nothing more than
+        today's records crosses the bus.  Memory, paid only with team_pick on the device route: a scratch buffer of one 8-byte
+        word per possible course point, (max_iter + 1 + the batch's path-point capacity) words for each of the N * K trees,
+        reserved at the first round and kept by the context (4.3 GiB for 4 096 AUVs x 4 trees at max_iter=2000; about a sixth of
+        what the trees' path points take); it grows with max_iter and with N * K, and where the device cannot provide it the
+        round raises AuvpError (a HIP allocation error).  ValueError, before any launch, without teams or for another value."""
         N = len(starts)
         sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
         labels = None if teams is None else team_labels(teams, N)
+        if team_pick is not None:
+            if team_pick != "claims":
+                raise ValueError("team_pick must be None or 'claims', not %r" % (team_pick,))
+            if labels is None:
+                raise ValueError("team_pick='claims' needs teams")
         K = int(trees_per_auv)
         if K < 1:
             raise ValueError("trees_per_auv must be >= 1")
@@ -528,7 +646,7 @@ class RRT:
             max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
         if commit == "device":
             return self._replanning_batch_device(starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight,
-                                                 max_iter, seeds, as_arrays, K, sets, labels)
+                                                 max_iter, seeds, as_arrays, K, sets, labels, team_pick)
         gens = [None] * N     # rngs[e]: the global stream of a sequential call
         streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
         for e in range(N):
@@ -554,7 +672,11 @@ class RRT:
                 if ttl[e] + last[e][4] > horizon_end:  # stays clipped for the later rounds too (:76-77)
                     ttl[e] = horizon_end - last[e][4]
             mtt = np.array([ttl[e] + last[e][4] for e in act], dtype=np.float64)
-            if K > 1:
+            claimed = [0] * len(act)
+            if team_pick is not None:
+                status, best_cost, tree, paths, claimed = self._replan_round_pick(act, K, streams, gens, last, all_habitats, hab, mtt, keep,
+                                                                                  weight, max_iter, labels, None if sets is None else sets[act])
+            elif K > 1:
                 status, best_cost, tree, paths = self._replan_round_best_of(act, K, streams, last, all_habitats, mtt, keep, weight,
                                                                             max_iter, None if sets is None else sets[act])
             else:
@@ -571,7 +693,7 @@ class RRT:
                 bucket = p[sel]
                 if as_arrays:
                     traj[e].append(bucket)
-                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(best_cost[i]), int(tree[i])))
+                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(best_cost[i]), int(tree[i]), claimed[i]))
                 else:
                     course = self._materialise_course(paths[i], last_obj[e])
                     objs = [course[j] for j in np.flatnonzero(sel)]
@@ -600,6 +722,8 @@ class RRT:
                                 round_max_traj_time=np.array([x[2] for x in r]),
                                 round_cost=np.array([x[3] for x in r]).reshape(-1, 4),
                                 round_tree=np.array([x[4] for x in r], dtype=np.int64), keep=keep[e], cost=costs[e]))
+                if team_pick is not None:
+                    res[-1]["round_claimed"] = np.array([x[5] for x in r], dtype=np.uint64)
             else:
                 c = costs[e]
                 res.append([traj[e], {k + 1: [b, hl] for k, (b, hl) in enumerate(rounds[e])},
@@ -625,7 +749,7 @@ class RRT:
         return costs
 
     def _replanning_batch_device(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter,
-                                 seeds, as_arrays, K, sets, labels=None):
+                                 seeds, as_arrays, K, sets, labels=None, team_pick=None):
         """replanning_batch with commit="device": per round one prepare + run, the winners' selection, and rrt_commit_kernel
         (Context.replan_commit; with team labels replan_team_kernel behind it: the records' keep is the team's); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
         drawing each active AUV's K round seeds from its random.Random."""
@@ -644,6 +768,8 @@ class RRT:
         ctx.replan_begin(last, keep)
         if labels is not None:
             ctx.replan_set_teams(labels)
+        # (a fleet without a team of two or more: everybody gets rrt_group_best's record, which is what it runs)
+        pick = team_pick is not None and len(team_csr(labels)[0]) > 1
         self._batch = None  # (rerank follows an exploring_batch only)
         log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
         while True:
@@ -663,7 +789,7 @@ class RRT:
                                   dist_to_end=self.dist_to_end, diff_max=self.diff_max, min_dist=0.5, max_plan_time=float(max_iter),
                                   habitat_keep=np.repeat(keep[act], K), summaries=False,
                                   shark_set=None if sets is None else np.repeat(sets[act], K))
-            best = ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
+            best = ctx.replan_team_pick(act, K) if pick else ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
             bad = best["status"] < 0
             if bad.any():
                 i = int(np.argmax(bad))
@@ -676,7 +802,8 @@ class RRT:
                 raise _lib.AuvpError(int(rec[i]["status"]), "AUV %d: the commit step failed on the device (status %d)" % (act[i], int(rec[i]["status"])))
             won = rec["winner"] >= 0
             alive[act[~won]] = False  # no qualifying leaf: the sequential call would raise TypeError
-            log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won]))
+            log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won],
+                        rec["claimed"][won] if pick else np.zeros(int(won.sum()), dtype=np.uint64)))
             last[act] = rec["last"]
             keep[act] = rec["keep"]
         if labels is not None:
@@ -695,9 +822,11 @@ class RRT:
             r_keep = np.concatenate([x[2] for x in log])[order]
             r_mtt = np.concatenate([x[3] for x in log])[order]
             r_tree = np.concatenate([x[4] for x in log])[order].astype(np.int64)
+            r_claimed = np.concatenate([x[5] for x in log])[order].astype(np.uint64)
             first = np.searchsorted(auv[order], np.arange(N + 1))
         else:
             r_rec, r_keep, r_mtt, r_tree = np.zeros(0, _lib.REPLAN_RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0, np.int64)
+            r_claimed = np.zeros(0, np.uint64)
             first = np.zeros(N + 1, dtype=np.int64)
         res = []
         for e in range(N):
@@ -710,6 +839,8 @@ class RRT:
                 res.append(dict(traj=rows[e], round_len=lens, round_keep=r_keep[a:b].copy(), round_max_traj_time=r_mtt[a:b].copy(),
                                 round_cost=r_rec["cost"][a:b].reshape(-1, 4).copy(), round_tree=r_tree[a:b].copy(),
                                 keep=int(keep[e]), cost=costs[e]))
+                if team_pick is not None:
+                    res[-1]["round_claimed"] = r_claimed[a:b].copy()
                 continue
             # objects: each round's first row is the previous round's last object (the start object in round 1), the rest are
             # new -- what _materialise_course makes of the course on the host route
@@ -730,28 +861,64 @@ class RRT:
                         [all_habitats[h] for h in range(H) if (int(keep[e]) >> h) & 1]])
         return res
 
-    def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
-        """one round of replanning_batch, one tree per active AUV: (status [A], best_cost [A,4], tree [A] = 0, courses)"""
-        round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
-        if all(gens[e] is None for e in act):
-            seed_arg = np.array([round_seeds[e] for e in act], dtype=np.uint64)
+    def _replan_round_summaries(self, act, K, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
+        """K trees per active AUV, run with summaries: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s, each from its
+        committed state with its horizon and list.  AUV e draws K round seeds from streams[e]; with K == 1 a generator gens[e]
+        continues the global stream instead and is advanced as exploring advances it.  A tree that failed on the device raises
+        AuvpError.  Returns (summaries [A*K], every tree's best course)."""
+        if K == 1:
+            round_seeds = {e: streams[e].getrandbits(63) for e in act if streams[e] is not None}
+            if all(gens[e] is None for e in act):
+                seed_arg = np.array([round_seeds[e] for e in act], dtype=np.uint64)
+            else:
+                st = [_mt_state_of(gens[e].getstate() if gens[e] is not None else random.Random(round_seeds[e]).getstate())
+                      for e in act]
+                seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
         else:
-            st = [_mt_state_of(gens[e].getstate() if gens[e] is not None else random.Random(round_seeds[e]).getstate())
-                  for e in act]
-            seed_arg = (np.stack([w for w, _ in st]), np.array([i for _, i in st], dtype=np.int32))
-        init_objs = [_Init(last[e]) for e in act]
-        summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, mtt, True, weight, max_iter, seed_arg,
-                                       [keep[e] for e in act], shark_set=sets)
-        for i, e in enumerate(act):
-            n = int(summ[i]["n_draw32"])
-            if gens[e] is not None and n:
-                gens[e].getrandbits(32 * n)  # what exploring does to the global stream
+            seed_arg = np.array([streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
+        init_objs = [_Init(last[e]) for e in act for _ in range(K)]
+        summ = self._explore_summaries(init_objs, all_habitats, 5, 2, True, np.repeat(mtt, K), True, weight, max_iter, seed_arg,
+                                       [keep[e] for e in act for _ in range(K)], shark_set=None if sets is None else np.repeat(sets, K))
+        if K == 1:
+            for i, e in enumerate(act):
+                n = int(summ[i]["n_draw32"])
+                if gens[e] is not None and n:
+                    gens[e].getrandbits(32 * n)  # what exploring does to the global stream
         bad = summ["status"] < 0
         if bad.any():
             i = int(np.argmax(bad))
-            raise _lib.AuvpError(int(summ[i]["status"]), "AUV %d failed on the device (status %d)" % (act[i], int(summ[i]["status"])))
-        paths = self._ctx.paths(summ)
+            raise _lib.AuvpError(int(summ[i]["status"]), ("a tree of AUV %d failed on the device (status %d)" if K > 1 else
+                                                          "AUV %d failed on the device (status %d)") % (act[i // K], int(summ[i]["status"])))
+        return summ, self._ctx.paths(summ)
+
+    def _replan_round(self, act, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
+        """one round of replanning_batch, one tree per active AUV: (status [A], best_cost [A,4], tree [A] = 0, courses)"""
+        summ, paths = self._replan_round_summaries(act, 1, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets)
         return summ["status"], summ["best_cost"], np.zeros(len(act), dtype=np.int64), paths
+
+    def _replan_round_pick(self, act, K, streams, gens, last, all_habitats, hab, mtt, keep, weight, max_iter, labels, sets=None):
+        """one round with team_pick="claims" on the host: K trees per active AUV, the round runs with summaries, EVERY candidate's
+        course is copied to the host and team_pick_claims chooses.  Returns as _replan_round, tree = the chosen member, the
+        courses the chosen ones', plus the claimed mask every AUV saw."""
+        summ, paths = self._replan_round_summaries(act, K, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets)
+        cands = []
+        for g, e in enumerate(act):
+            row = []
+            for k in range(K):
+                s, p = summ[g * K + k], paths[g * K + k]
+                if s["best_leaf"] < 0 or len(p) == 0:
+                    row.append(None)
+                    continue
+                p = p.copy()
+                p[0] = last[e]  # (row 0 is the committed state, as in the commit rule)
+                row.append(dict(words=course_habitat_words(p[:, :2], p[:, 4], self._bins, 0, len(self._bins), hab),
+                                cost=[float(x) for x in s["best_cost"]], leaf_time=float(p[-1, 4])))
+            cands.append(row)
+        picks = team_pick_claims(labels, keep, act, cands, weight)
+        win = [r["winner"] for r in picks]
+        status = np.array([_lib.OK if w >= 0 else _lib.NO_QUALIFYING_LEAF for w in win], dtype=np.int32)
+        return (status, np.array([r["cost"] for r in picks], dtype=np.float64).reshape(-1, 4), np.array(win, dtype=np.int64),
+                [paths[g * K + w] if w >= 0 else np.zeros((0, 7)) for g, w in enumerate(win)], [r["claimed"] for r in picks])
 
     def _replan_round_best_of(self, act, K, streams, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
         """one round with K trees per active AUV: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s members; the winners are

@@ -222,7 +222,9 @@ typedef struct {
   double cost[4];      /* the winner's best_cost (inf without one) */
   double last[7];      /* the AUV's state after the round */
   uint64_t keep;       /* the AUV's list after the round; with teams (auvp_replan_set_teams): its team's list after the round */
-  double _reserved[2];
+  uint64_t claimed;    /* after auvp_replan_team_pick: the habitats the AUV's teammates had claimed when its winner was chosen
+                        * (0 for an AUV without a teammate, and after auvp_rrt_group_best) */
+  double _reserved;
 } auvp_replan_record; /* 128 bytes */
 /* A fleet's state on the handle: last = start7 [n_auvs,7], keep = keep0 [n_auvs] (keep_is_shared != 0: keep0[0] for everyone),
  * an empty log, zeroed counters.  It survives auvp_rrt_prepare*, auvp_rrt_run, auvp_world_set_habitats and
@@ -248,6 +250,40 @@ int auvp_replan_team_fold(auvp_handle* h, int32_t n, const int32_t* team_of, uin
  * [0, n_auvs), an AUV named twice, round_span not > 0.  A call that fails launches nothing and changes no state. */
 int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of /* [n_active] */, double round_span,
                        auvp_replan_record* out /* [n_active], may be NULL */);
+/* The team-aware winner selection ("claims", csrc/replan_pick.h), in place of auvp_rrt_group_best in a round: the batch that
+ * just ran holds K trees for each of n_active AUVs, group g = episodes g*K .. g*K+K-1 = AUV auv_of[g].  Every group first gets
+ * rrt_group_best_kernel's record.  Then, for every team of two or more (auvp_replan_set_teams), the members that are part of
+ * the round are taken in ascending AUV index with claimed = 0: each tree's own best course (as the leaf pass ranked it under the
+ * member's keep) is scored again under keep & ~claimed -- the habitat terms of habitat_shark_cost_func against the shorter list,
+ * the shark term unchanged --, the winner is rrt_group_best's fold over these scores, and the habitats its whole course visits
+ * under that mask join claimed.  The members' records carry that winner and its score (cost[4]); the others are untouched.  With
+ * claimed == 0 the score is the summary's best_cost bit for bit.  Three launches on the handle's stream (rrt_group_best_kernel,
+ * rrt_course_words_kernel: one 64-bit word per course point into a scratch buffer sized from the batch's capacities,
+ * replan_team_pick_kernel: one wavefront per team), one copy of the records; auvp_replan_commit, auvp_rrt_group_paths and
+ * auvp_replan_traj work behind it as behind auvp_rrt_group_best, and the commit's records carry `claimed`.  out [n_active] may
+ * be NULL.  AUVP_ERR_STATE: no auvp_replan_begin, no teams, or no batch that has run.  AUVP_ERR_ARG: n_active * K is not the
+ * batch's size, an AUV outside the fleet or named twice.  A call that fails launches nothing and leaves the fleet and the
+ * group records as they were.
+ * The scratch buffer: (cap_nodes + cap_points) 8-byte words for each of the batch's episodes, reserved by the first call and
+ * kept by the handle (4.3 GiB for 16 384 episodes of 2 000 iterations); only callers of this entry point pay for it.
+ * Caveat: the commit recognises "the group records are still this call's" by comparing the handle's records with the copy this
+ * call kept.  An auvp_rrt_group_best on the SAME batch between this call and auvp_replan_commit that happens to produce
+ * byte-identical records (no claim touched any member's list) is therefore not told apart, and that commit's records carry
+ * this call's claimed masks instead of 0.  Call one of the two per round. */
+int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_of /* [n_active] */, int32_t K,
+                          struct auvp_rrt_group_best* out /* [n_active], may be NULL */);
+/* Probe: the same three kernels on the caller's candidates, against the world's habitat table and time bins.  n_auvs AUVs with
+ * labels team_of and lists keep; group g of n_active is AUV auv_of[g] and has K candidates, candidate e = g*K + k: its course is
+ * rows course_off[e] .. course_off[e+1]-1 of courses_xyt [*,3] (x, y, traj_time; none: a tree without a leaf; row 0 is taken
+ * as given), cost4 [E,4] its cost as the leaf pass would report it (cost4[.,3] is the shark term that stays), leaf_t [E] its
+ * leaf's time, length [E] (may be NULL: 0) its path length, and bin_lo / bin_hi [E] the shark bins lo .. hi-1 that exploring
+ * selects for its leaf.  weights3: w1, w2, w3.  out [n_active] gets the group records, claimed_out [n_active] the mask each
+ * group's AUV saw.  The fleet of auvp_replan_begin and the handle's group records are not touched. */
+int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                  const int32_t* auv_of, int32_t K, const int64_t* course_off /* [n_active*K+1] */,
+                                  const double* courses_xyt, const double* cost4, const double* leaf_t, const double* length,
+                                  const int32_t* bin_lo, const int32_t* bin_hi, const double* weights3,
+                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out);
 /* Every AUV's whole committed trajectory, in round order: AUV a's rows are row_off[a] .. row_off[a+1]-1 of rows [*,7].  The only
  * bulk copy to the host (one gather launch, one copy of rows * 56 bytes).  rows == NULL: row_off [n_auvs+1] alone, to size the
  * buffer.  AUVP_ERR_STATE without auvp_replan_begin. */
@@ -262,7 +298,7 @@ int auvp_replan_commit_courses(auvp_handle* h, int32_t n_states, const int64_t* 
 /* Counters since auvp_replan_begin (each pointer may be NULL): the fleet's size (0: none), rounds committed, rows in the log,
  * the bytes the auvp_replan_* entry points have copied to the host, the part of those that auvp_replan_traj copied, and
  * rrt_commit_kernel's time summed over the rounds (HIP events, milliseconds; with teams set the span covers
- * replan_team_kernel too). */
+ * replan_team_kernel too, and auvp_replan_team_pick adds the time of its two own kernels). */
 int auvp_replan_info(auvp_handle* h, int32_t* n_auvs, int32_t* rounds, int64_t* rows, int64_t* bytes_to_host, int64_t* bytes_traj,
                      double* commit_ms);
 
