@@ -57,7 +57,8 @@ assert GROUP_BEST_DTYPE.itemsize == C.sizeof(RRTGroupBest)
 
 # auvp_replan_record (include/auvplan.h): one AUV's round of the device commit step
 REPLAN_RECORD_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_committed", "<i4"), ("path_len", "<i4"),
-                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("claimed", "<u8"), ("_reserved", "<f8")])
+                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("claimed", "<u8"), ("conflicts", "<i4"),
+                                ("_reserved", "<i4")])
 assert REPLAN_RECORD_DTYPE.itemsize == 128
 
 MODES = {"timebin": 0, "plantime": 1, "nn": 2}
@@ -152,6 +153,10 @@ def load():
         L.auvp_replan_team_pick.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_void_p]
         L.auvp_replan_team_pick_courses.argtypes = [vp, C.c_int32, _ip, _u64p, C.c_int32, _ip, C.c_int32, _i64p, _dp, _dp, _dp, _dp,
                                                     _ip, _ip, _dp, C.c_void_p, _u64p]
+    if hasattr(L, "auvp_replan_team_pick_apart"):  # (likewise: the selection that keeps teammates' courses apart)
+        L.auvp_replan_team_pick_apart.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+        L.auvp_replan_team_pick_apart_courses.argtypes = [vp, C.c_int32, _ip, _u64p, C.c_int32, _ip, C.c_int32, _i64p, _dp, _dp, _dp, _dp,
+                                                          _ip, _ip, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, _u64p, _ip]
     L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
     L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
     L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
@@ -620,10 +625,29 @@ class Context:
         self._chk(self.L.auvp_replan_team_pick(self.h, len(a), _p(a, _ip), int(K), out.ctypes.data_as(C.c_void_p)))
         return out[:len(a)]
 
-    def replan_team_pick_courses(self, team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights):
+    def replan_team_pick_apart(self, auv_of, K, use_claims, d, tick, W):
+        """the winner selection that keeps teammates' courses apart, in place of rrt_group_best / replan_team_pick
+        (auvp_replan_team_pick_apart): d metres, tick seconds, W ticks per course; use_claims: the scores under the teammates'
+        claims, as replan_team_pick's.  Returns [n_active] GROUP_BEST_DTYPE records; the conflict counts come back in the
+        records of the replan_commit behind it."""
+        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
+        self._chk(self.L.auvp_replan_team_pick_apart(self.h, len(a), _p(a, _ip), int(K), 1 if use_claims else 0, float(d), float(tick), int(W),
+                                                     out.ctypes.data_as(C.c_void_p)))
+        return out[:len(a)]
+
+    def replan_team_pick_apart_courses(self, team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights,
+                                       use_claims, d, tick, W):
+        """probe: replan_team_pick_courses with rrt_course_ticks_kernel and replan_team_pick_apart_kernel on the caller's
+        candidates.  Returns (records [n_active], claimed [n_active], conflicts [n_active])."""
+        return self.replan_team_pick_courses(team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights,
+                                             apart=(1 if use_claims else 0, float(d), float(tick), int(W)))
+
+    def replan_team_pick_courses(self, team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights, apart=None):
         """probe: rrt_group_best_kernel, rrt_course_words_kernel and replan_team_pick_kernel on the caller's candidates against
         the world's habitat table and time bins.  courses_xyt: n_active * K arrays [L,3] (L == 0: a tree without a leaf), in
-        group order; cost4 [E,4], leaf_t [E], length [E], bin_lo / bin_hi [E].  Returns (records [n_active], claimed [n_active])."""
+        group order; cost4 [E,4], leaf_t [E], length [E], bin_lo / bin_hi [E].  Returns (records [n_active], claimed [n_active]).
+        apart: replan_team_pick_apart_courses' arguments."""
         t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
         kp = np.array(keep, dtype=np.uint64).reshape(-1)
         a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
@@ -642,6 +666,13 @@ class Context:
         out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
         claimed = np.zeros(max(len(a), 1), dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
+        if apart is not None:
+            conflicts = np.zeros(max(len(a), 1), dtype=np.int32)
+            self._chk(self.L.auvp_replan_team_pick_apart_courses(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(u64p), len(a), _p(a, _ip), int(K),
+                                                                 off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(c4), _p(lt), _p(ln),
+                                                                 _p(lo, _ip), _p(hi, _ip), _p(w), apart[0], apart[1], apart[2], apart[3],
+                                                                 out.ctypes.data_as(C.c_void_p), claimed.ctypes.data_as(u64p), _p(conflicts, _ip)))
+            return out[:len(a)], claimed[:len(a)], conflicts[:len(a)]
         self._chk(self.L.auvp_replan_team_pick_courses(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(u64p), len(a), _p(a, _ip), int(K),
                                                        off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(c4), _p(lt), _p(ln),
                                                        _p(lo, _ip), _p(hi, _ip), _p(w), out.ctypes.data_as(C.c_void_p),
@@ -686,8 +717,8 @@ class Context:
 
     def replan_info(self):
         """counters since replan_begin: n_auvs, rounds, rows, bytes_to_host (what the replan entry points copied to the host),
-        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, with teams replan_team_kernel's too, and with replan_team_pick
-        rrt_course_words_kernel's and replan_team_pick_kernel's, summed)"""
+        bytes_traj (replan_traj's part of it), commit_ms (rrt_commit_kernel's time, with teams replan_team_kernel's too, with replan_team_pick
+        rrt_course_words_kernel's and replan_team_pick_kernel's, and with replan_team_pick_apart its kernels', summed)"""
         a, r = C.c_int32(0), C.c_int32(0)
         rows, b, bt, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         self._chk(self.L.auvp_replan_info(self.h, C.byref(a), C.byref(r), C.byref(rows), C.byref(b), C.byref(bt), C.byref(ms)))

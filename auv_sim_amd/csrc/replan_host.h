@@ -2,7 +2,9 @@
 // state on the handle (last [n,7], keep [n], the trajectory log, the teams), the launch of rrt_commit_kernel (replan_kernels.hip)
 // behind auvp_rrt_group_best and of replan_team_kernel behind it where the fleet has teams, the one download at the end, and the
 // probe entries that run the kernels' rules on the caller's courses and masks; and the team-aware winner selection
-// (auvp_replan_team_pick: rrt_group_best_kernel, rrt_course_words_kernel, replan_team_pick_kernel -- replan_pick.h).
+// (auvp_replan_team_pick: rrt_group_best_kernel, rrt_course_words_kernel, replan_team_pick_kernel -- replan_pick.h) and the one
+// that keeps teammates' courses apart (auvp_replan_team_pick_apart: rrt_course_ticks_kernel, replan_team_pick_apart_kernel --
+// replan_apart.h).
 // Every index the kernel uses is computed here from host data: the group records' host copy (h->group_best) sizes the course
 // scratch and the round's log space before the launch.
 // Included at the end of auvplan.hip.
@@ -11,7 +13,10 @@
 #include "replan_commit.h"
 #include "replan_teams.h"
 #include "replan_pick.h"
+#include "replan_apart.h"
 
+extern "C" hipError_t auvpi_replan_ticks_launch(const auvp::RrtBuffers* B, const auvp::ReplanTicksDev* A, hipStream_t stream);
+extern "C" hipError_t auvpi_replan_pick_apart_launch(const auvp::ReplanPickDev* T, const auvp::ReplanApartDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_pick_launch(const auvp::ReplanPickDev* T, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_team_launch(const auvp::ReplanTeamDev* T, hipStream_t stream);
@@ -22,6 +27,10 @@ static_assert(sizeof(auvp_replan_record) == sizeof(auvp::ReplanRecord), "round r
 // the public record's `claimed` is the first of the internal record's two reserved doubles
 static_assert(offsetof(auvp_replan_record, claimed) == offsetof(auvp::ReplanRecord, _reserved), "round record layout: claimed");
 static_assert(offsetof(auvp_replan_record, keep) == offsetof(auvp::ReplanRecord, keep), "round record layout: keep");
+// ... and `conflicts` with its own reserved word the second
+static_assert(offsetof(auvp_replan_record, conflicts) == offsetof(auvp::ReplanRecord, _reserved) + sizeof(double), "round record layout: conflicts");
+static_assert(sizeof(((auvp_replan_record*)nullptr)->conflicts) + sizeof(((auvp_replan_record*)nullptr)->_reserved) == sizeof(double),
+              "round record layout: conflicts");
 
 namespace {
 
@@ -36,10 +45,11 @@ struct ReplanState {
   std::vector<Piece> pieces;               // in round order
   std::vector<auvp::ReplanRecord> rec_host;
   long long bytes_to_host = 0, bytes_traj = 0;
-  double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's; with auvp_replan_team_pick: and
-                                           // its two kernels'), summed over the rounds
+  double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's; with auvp_replan_team_pick /
+                                           // _apart: and its kernels'), summed over the rounds
   // the fleet's teams (auvp_replan_set_teams): the CSR of replan_teams.h in HBM; n_teams == 0: none, nothing more is launched
   int n_teams = 0;
+  int max_team = 0;                        // members of the largest team
   DevBuf team_off, team_members, slot_of;
   // the team-aware selection (auvp_replan_team_pick) of the round being committed: the masks the members saw, [pick_best.size()]
   // in HBM, and the group records it left -- the commit copies the masks into its records only if the handle's group records
@@ -47,6 +57,10 @@ struct ReplanState {
   DevBuf words, leaf_t, claimed, pick_auv, pick_slot_of;
   std::vector<RrtGroupBest> pick_best;
   bool pick_pending = false;
+  // auvp_replan_team_pick_apart: every episode's tick table and the winners' conflict counts [pick_best.size()], which the
+  // commit copies as it copies the masks
+  DevBuf tick_head, tick_xy, conflicts;
+  bool pick_apart = false;
 };
 
 ReplanState* replan_of(auvp_handle* h) {
@@ -101,9 +115,14 @@ int replan_launch(auvp_handle* h, ReplanState& S, const auvp::RrtBuffers* B, auv
     // the masks of auvp_replan_team_pick into the records' `claimed`, device to device, if the group records are still its
     S.pick_pending = false;
     if (S.pick_best.size() == slots.size() && h->group_best.size() == slots.size() &&
-        memcmp(S.pick_best.data(), h->group_best.data(), slots.size() * sizeof(RrtGroupBest)) == 0)
+        memcmp(S.pick_best.data(), h->group_best.data(), slots.size() * sizeof(RrtGroupBest)) == 0) {
       HIPCHK(h, hipMemcpy2DAsync(reinterpret_cast<char*>(S.rec.p) + offsetof(auvp::ReplanRecord, _reserved), sizeof(auvp::ReplanRecord), S.claimed.p,
                                  sizeof(uint64_t), sizeof(uint64_t), slots.size(), hipMemcpyDeviceToDevice, h->stream));
+      if (S.pick_apart)  // (the counts of auvp_replan_team_pick_apart into `conflicts`, the low half of the second reserved word)
+        HIPCHK(h, hipMemcpy2DAsync(reinterpret_cast<char*>(S.rec.p) + offsetof(auvp::ReplanRecord, _reserved) + sizeof(double),
+                                   sizeof(auvp::ReplanRecord), S.conflicts.p, sizeof(int32_t), sizeof(int32_t), slots.size(),
+                                   hipMemcpyDeviceToDevice, h->stream));
+    }
   }
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   S.rec_host.resize(slots.size());
@@ -139,6 +158,7 @@ int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, cons
   S.bytes_to_host = S.bytes_traj = 0;
   S.commit_ms = 0.0;
   S.n_teams = 0;  // (the teams were the old fleet's)
+  S.max_team = 0;
   S.pick_pending = false;
   S.n_auvs = n_auvs;
   return AUVP_OK;
@@ -150,9 +170,9 @@ int auvp_replan_set_teams(auvp_handle* h, int32_t n_auvs, const int32_t* team_of
   if (!Sp || Sp->n_auvs < 1) return fail(h, AUVP_ERR_STATE, "auvp_replan_begin not called");
   ReplanState& S = *Sp;
   if (n_auvs != S.n_auvs) return fail(h, AUVP_ERR_ARG, "n_auvs %d, the fleet has %d", n_auvs, S.n_auvs);
-  if (!team_of) { S.n_teams = 0; return AUVP_OK; }
+  if (!team_of) { S.n_teams = 0; S.max_team = 0; return AUVP_OK; }
   const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
-  if (csr.n_teams() == 0) { S.n_teams = 0; return AUVP_OK; }
+  if (csr.n_teams() == 0) { S.n_teams = 0; S.max_team = 0; return AUVP_OK; }
   HIPCHK(h, hipSetDevice(h->device));
   // into buffers of their own, swapped in once both tables are there: a call that fails leaves the teams as they were
   DevBuf off, mem;
@@ -163,6 +183,8 @@ int auvp_replan_set_teams(auvp_handle* h, int32_t n_auvs, const int32_t* team_of
   std::swap(S.team_off.p, off.p); std::swap(S.team_off.cap, off.cap);
   std::swap(S.team_members.p, mem.p); std::swap(S.team_members.cap, mem.cap);
   S.n_teams = csr.n_teams();
+  S.max_team = 0;
+  for (int t = 0; t < csr.n_teams(); t++) S.max_team = std::max(S.max_team, (int)(csr.team_off[(size_t)t + 1] - csr.team_off[(size_t)t]));
   return AUVP_OK;
 }
 
@@ -249,7 +271,28 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
   return AUVP_OK;
 }
 
-int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, struct auvp_rrt_group_best* out) {
+}  // extern "C"
+
+namespace {
+
+// team_separation's arguments (replan_apart.h); null: the selection by the claims alone
+struct ReplanApartArgs {
+  int32_t use_claims, W;
+  double d, tick;
+};
+
+int replan_apart_check(auvp_handle* h, const ReplanApartArgs* ap, int max_team) {
+  if (!ap) return AUVP_OK;
+  if (!auvp::replan_apart_args_ok(ap->d, ap->tick, ap->W))
+    return fail(h, AUVP_ERR_ARG, "need a finite d > 0, a finite tick > 0 and W in 1 .. %d", auvp::REPLAN_APART_MAX_TICKS);
+  if (max_team > auvp::REPLAN_APART_MAX_TEAM)
+    return fail(h, AUVP_ERR_ARG, "a team of %d members, more than %d", max_team, auvp::REPLAN_APART_MAX_TEAM);
+  return AUVP_OK;
+}
+
+// auvp_replan_team_pick (ap == null) and auvp_replan_team_pick_apart
+int replan_team_pick_impl(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, const ReplanApartArgs* ap,
+                          struct auvp_rrt_group_best* out) {
   if (!h) return AUVP_ERR_ARG;
   ReplanState* Sp = static_cast<ReplanState*>(h->replan);
   if (!Sp || Sp->n_auvs < 1) return fail(h, AUVP_ERR_STATE, "auvp_replan_begin not called");
@@ -260,6 +303,9 @@ int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   const int E = h->E;
   if ((long long)n_active * K != (long long)E) return fail(h, AUVP_ERR_ARG, "the batch has %d episodes, not %d x %d", E, n_active, K);
   const int G = n_active;
+  int rc;
+  if ((rc = replan_apart_check(h, ap, S.max_team))) return rc;
+  const bool words = !ap || ap->use_claims;  // (without the claims nobody reads the words: no launch, no scratch for them)
   std::vector<int32_t> slot_of((size_t)S.n_auvs, -1);
   for (int g = 0; g < G; g++) {
     const int a = auv_of[g];
@@ -273,17 +319,22 @@ int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   // a course has at most one element per node and per path point of its tree: the scratch is sized from the batch's capacities
   // (the summaries stay in HBM), the same place for every episode
   const int64_t stride = (int64_t)h->B.cap_nodes + (int64_t)h->B.cap_points;
-  HIPCHK(h, S.words.reserve((size_t)E * (size_t)stride * sizeof(uint64_t)));
+  if (words) HIPCHK(h, S.words.reserve((size_t)E * (size_t)stride * sizeof(uint64_t)));
   HIPCHK(h, S.leaf_t.reserve((size_t)E * sizeof(double)));
   HIPCHK(h, S.claimed.reserve((size_t)G * sizeof(uint64_t)));
+  if (ap) {
+    HIPCHK(h, S.tick_head.reserve((size_t)E * 2 * sizeof(int32_t)));
+    HIPCHK(h, S.tick_xy.reserve((size_t)E * (size_t)ap->W * 2 * sizeof(double)));
+    HIPCHK(h, S.conflicts.reserve((size_t)G * sizeof(int32_t)));
+  }
   h->have_group = false;
   S.pick_pending = false;
-  int rc;
   if ((rc = upload(h, h->d_group_off, group_off.data(), group_off.size()))) return rc;
   if ((rc = upload(h, S.pick_auv, auv_of, (size_t)G))) return rc;
   if ((rc = upload(h, S.pick_slot_of, slot_of.data(), slot_of.size()))) return rc;
   HIPCHK(h, h->d_group_best.reserve((size_t)G * sizeof(RrtGroupBest)));
   HIPCHK(h, hipMemsetAsync(S.claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
+  if (ap) HIPCHK(h, hipMemsetAsync(S.conflicts.p, 0, (size_t)G * sizeof(int32_t), h->stream));
   auvp::ReplanWordsDev A{};
   A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
   A.stride = stride;
@@ -298,13 +349,27 @@ int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   T.words = A.words; T.stride = stride; T.leaf_t = A.leaf_t;
   T.best = h->d_group_best.as<RrtGroupBest>(); T.claimed = S.claimed.as<uint64_t>();
   T.w1 = h->P.w[0]; T.w2 = h->P.w[1];
+  auvp::ReplanTicksDev C{};
+  auvp::ReplanApartDev D{};
+  if (ap) {
+    C.n_episodes = E; C.K = K; C.W = ap->W; C.tick = ap->tick;
+    C.auv_of = A.auv_of; C.last = A.last;
+    C.head = S.tick_head.as<int32_t>(); C.xy = S.tick_xy.as<double>();
+    D.W = ap->W; D.use_claims = ap->use_claims ? 1 : 0; D.d2 = ap->d * ap->d;
+    D.head = C.head; D.xy = C.xy; D.conflicts = S.conflicts.as<int32_t>();
+  }
   // every group gets rrt_group_best_kernel's record; the pick rewrites those of the members of teams of two or more
   hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
                      h->B.summary, h->d_group_off.as<int32_t>(), h->d_group_best.as<RrtGroupBest>(), G);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  HIPCHK(h, auvpi_replan_words_launch(&h->B, &A, h->stream));
-  HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  if (words) HIPCHK(h, auvpi_replan_words_launch(&h->B, &A, h->stream));
+  if (ap) {
+    HIPCHK(h, auvpi_replan_ticks_launch(&h->B, &C, h->stream));
+    HIPCHK(h, auvpi_replan_pick_apart_launch(&T, &D, h->stream));
+  } else {
+    HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  }
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   h->group_best.resize((size_t)G);
   HIPCHK(h, hipMemcpyAsync(h->group_best.data(), h->d_group_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
@@ -315,15 +380,62 @@ int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
   S.pick_best = h->group_best;
   S.pick_pending = true;
+  S.pick_apart = ap != nullptr;
   h->have_group = true;
   if (out) memcpy(out, h->group_best.data(), (size_t)G * sizeof(RrtGroupBest));
   return AUVP_OK;
+}
+
+// auvp_replan_team_pick_courses (ap == null) and auvp_replan_team_pick_apart_courses
+int replan_team_pick_courses_impl(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                  const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
+                                  const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
+                                  const int32_t* bin_hi, const double* weights3, const ReplanApartArgs* ap,
+                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out);
+
+}  // namespace
+
+extern "C" {
+
+int auvp_replan_team_pick(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, struct auvp_rrt_group_best* out) {
+  return replan_team_pick_impl(h, n_active, auv_of, K, nullptr, out);
+}
+
+int auvp_replan_team_pick_apart(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, int32_t use_claims, double d, double tick,
+                                int32_t W, struct auvp_rrt_group_best* out) {
+  const ReplanApartArgs ap{use_claims, W, d, tick};
+  return replan_team_pick_impl(h, n_active, auv_of, K, &ap, out);
 }
 
 int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
                                   const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
                                   const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
                                   const int32_t* bin_hi, const double* weights3, struct auvp_rrt_group_best* out, uint64_t* claimed_out) {
+  return replan_team_pick_courses_impl(h, n_auvs, team_of, keep, n_active, auv_of, K, course_off, courses_xyt, cost4, leaf_t, length, bin_lo,
+                                       bin_hi, weights3, nullptr, out, claimed_out, nullptr);
+}
+
+int auvp_replan_team_pick_apart_courses(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                        const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
+                                        const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
+                                        const int32_t* bin_hi, const double* weights3, int32_t use_claims, double d, double tick, int32_t W,
+                                        struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!conflicts_out) return fail(h, AUVP_ERR_ARG, "bad probe arguments");
+  const ReplanApartArgs ap{use_claims, W, d, tick};
+  return replan_team_pick_courses_impl(h, n_auvs, team_of, keep, n_active, auv_of, K, course_off, courses_xyt, cost4, leaf_t, length, bin_lo,
+                                       bin_hi, weights3, &ap, out, claimed_out, conflicts_out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int replan_team_pick_courses_impl(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                  const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
+                                  const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
+                                  const int32_t* bin_hi, const double* weights3, const ReplanApartArgs* ap,
+                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out) {
   if (!h) return AUVP_ERR_ARG;
   if (n_auvs < 1 || n_active < 1 || K < 1 || !team_of || !keep || !auv_of || !course_off || !cost4 || !leaf_t || !bin_lo || !bin_hi ||
       !weights3 || !out || !claimed_out)
@@ -361,10 +473,12 @@ int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t*
   }
   for (int g = 0; g <= G; g++) group_off[(size_t)g] = (int32_t)(g * K);
   const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
+  int rc, max_team = 0;
+  for (int t = 0; t < csr.n_teams(); t++) max_team = std::max(max_team, (int)(csr.team_off[(size_t)t + 1] - csr.team_off[(size_t)t]));
+  if ((rc = replan_apart_check(h, ap, max_team))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   // the probe's own buffers: the fleet's state, the handle's group records and the counters stay as they are
-  DevBuf d_summ, d_len, d_goff, d_off, d_xyt, d_lt, d_lo, d_hi, d_keep, d_slot, d_toff, d_tmem, d_words, d_best, d_claimed;
-  int rc;
+  DevBuf d_summ, d_len, d_goff, d_off, d_xyt, d_lt, d_lo, d_hi, d_keep, d_slot, d_toff, d_tmem, d_words, d_best, d_claimed, d_thead, d_txy, d_conf;
   if ((rc = upload(h, d_summ, summ.data(), summ.size()))) return rc;
   if ((rc = upload(h, d_len, len.data(), len.size()))) return rc;
   if ((rc = upload(h, d_goff, group_off.data(), group_off.size()))) return rc;
@@ -381,6 +495,19 @@ int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t*
   HIPCHK(h, d_best.reserve((size_t)G * sizeof(RrtGroupBest)));
   HIPCHK(h, d_claimed.reserve((size_t)G * sizeof(uint64_t)));
   HIPCHK(h, hipMemsetAsync(d_claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
+  auvp::ReplanTicksDev C{};
+  auvp::ReplanApartDev D{};
+  if (ap) {
+    HIPCHK(h, d_thead.reserve((size_t)E * 2 * sizeof(int32_t)));
+    HIPCHK(h, d_txy.reserve((size_t)E * (size_t)ap->W * 2 * sizeof(double)));
+    HIPCHK(h, d_conf.reserve((size_t)G * sizeof(int32_t)));
+    HIPCHK(h, hipMemsetAsync(d_conf.p, 0, (size_t)G * sizeof(int32_t), h->stream));
+    C.n_episodes = E; C.K = K; C.W = ap->W; C.from_courses = 1; C.tick = ap->tick;
+    C.off = d_off.as<int64_t>(); C.xyt = d_xyt.as<double>(); C.len = d_len.as<int32_t>();
+    C.head = d_thead.as<int32_t>(); C.xy = d_txy.as<double>();
+    D.W = ap->W; D.use_claims = ap->use_claims ? 1 : 0; D.d2 = ap->d * ap->d;
+    D.head = C.head; D.xy = C.xy; D.conflicts = d_conf.as<int32_t>();
+  }
   auvp::ReplanWordsDev A{};
   A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
   A.from_courses = 1;
@@ -401,16 +528,26 @@ int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t*
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, auvpi_replan_words_launch(nullptr, &A, h->stream));
-  HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  if (ap) {
+    HIPCHK(h, auvpi_replan_ticks_launch(nullptr, &C, h->stream));
+    HIPCHK(h, auvpi_replan_pick_apart_launch(&T, &D, h->stream));
+  } else {
+    HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  }
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   HIPCHK(h, hipMemcpyAsync(out, d_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(claimed_out, d_claimed.p, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  if (ap) HIPCHK(h, hipMemcpyAsync(conflicts_out, d_conf.p, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
   return AUVP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int auvp_replan_traj(auvp_handle* h, int64_t* row_off, double* rows) {
   if (!h) return AUVP_ERR_ARG;

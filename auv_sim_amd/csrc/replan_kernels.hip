@@ -8,6 +8,7 @@
 //   replan_team_kernel  one wavefront per team (replan_teams.h): every member's keep becomes the AND of the members' masks,
 //                       in the state array and in the round's records
 //   rrt_course_words_kernel, replan_team_pick_kernel  the team-aware winner selection (replan_pick.h), see below
+//   rrt_course_ticks_kernel, replan_team_pick_apart_kernel  the selection that keeps teammates' courses apart (replan_apart.h)
 //
 // Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "replan_commit.h"
 #include "replan_teams.h"
 #include "replan_pick.h"
+#include "replan_apart.h"
 #include "rrt_course_walk.h"
 
 namespace auvp {
@@ -281,7 +283,190 @@ static __global__ __launch_bounds__(REPLAN_PICK_WAVES * 64) void replan_team_pic
   }
 }
 
+// ---- team_separation (replan_apart.h) ------------------------------------------------------------------------------------------
+//
+// rrt_course_ticks_kernel: one wavefront (= one workgroup) per candidate episode; its tick table (s_lo, n, xy [n,2]) into a
+// scratch buffer in HBM.  This is the parallel part: E courses with nothing dependent between them.  The walk of the course has
+// every row on exactly one lane and a row needs no neighbour: it proposes its index for its own tick with an LDS atomic max
+// (the largest row of a tick owns it); a second walk lets the row that won its tick deposit its position there; a prefix max
+// over the ticks, 64 at a time, then gives every tick its owner -- the key is (row << 32 | tick the row proposed), so the
+// position is read from the owner's own tick.  LDS: W * (4 + 16) bytes, at most 20 KB.  An episode without a leaf, or one whose
+// row 0 has no tick inside int32, gets the empty table.
+static __global__ __launch_bounds__(64) void rrt_course_ticks_kernel(RrtBuffers B, ReplanTicksDev A) {
+  __shared__ int s_prop[REPLAN_APART_MAX_TICKS];
+  __shared__ double s_xy[2 * REPLAN_APART_MAX_TICKS];
+  __shared__ int s_top;
+  const int ep = blockIdx.x;
+  if (ep >= A.n_episodes) return;  // (the whole workgroup)
+  const int lane = lane_id();
+  const int W = A.W < REPLAN_APART_MAX_TICKS ? (A.W > 1 ? A.W : 1) : REPLAN_APART_MAX_TICKS;
+  const double tick = A.tick;
+  int32_t* head = A.head + 2 * (size_t)ep;
+  double* out = A.xy + 2 * (size_t)ep * (size_t)A.W;
+  int L = 0;
+  const double* c = nullptr;     // the probe: the caller's course
+  const double* last = nullptr;  // the batch: the AUV's committed state
+  if (A.from_courses) {
+    L = A.len[ep];
+    c = A.xyt + 3 * (size_t)A.off[ep];
+  } else {
+    const RrtSummary* s = B.summary + ep;
+    L = s->best_leaf >= 0 ? s->best_path_len : 0;
+    last = A.last + (size_t)REPLAN_ROW * (size_t)A.auv_of[ep / A.K];
+  }
+  const double q0 = L >= 1 ? replan_tick_q(A.from_courses ? c[2] : last[4], tick) : __builtin_nan("");
+  if (!replan_tick_base_ok(q0)) {  // (the same on every lane)
+    if (lane == 0) { head[0] = 0; head[1] = 0; }
+    return;
+  }
+  for (int j = lane; j < W; j += 64) s_prop[j] = -1;
+  if (lane == 0) s_top = 0;
+  __syncthreads();
+  int top = 0;
+  auto slot_of = [&](double t) { return replan_tick_slot(replan_tick_q(t, tick), q0, W); };
+  auto propose = [&](int at, double t) {
+    const int s = slot_of(t);
+    if (s < 0) return;
+    if (s >= W) { top = W - 1; return; }
+    top = s > top ? s : top;
+    atomicMax(&s_prop[s], at);
+  };
+  auto deposit = [&](int at, double x, double y, double t) {
+    const int s = slot_of(t);
+    if (s < 0 || s >= W || s_prop[s] != at) return;
+    s_xy[2 * s] = x; s_xy[2 * s + 1] = y;
+  };
+  if (A.from_courses) {
+    for (int i = lane; i < L; i += 64) propose(i, c[3 * (size_t)i + 2]);
+  } else {
+    rrt_course_walk_xyt(B, ep, [&](int at, double x, double y, double t) {
+      if (at < 0 || at >= L) return;
+      propose(at, at == 0 ? last[4] : t);
+    });
+  }
+  atomicMax(&s_top, top);
+  __syncthreads();
+  if (A.from_courses) {
+    for (int i = lane; i < L; i += 64) deposit(i, c[3 * (size_t)i], c[3 * (size_t)i + 1], c[3 * (size_t)i + 2]);
+  } else {
+    rrt_course_walk_xyt(B, ep, [&](int at, double x, double y, double t) {
+      if (at < 0 || at >= L) return;
+      if (at == 0) { x = last[0]; y = last[1]; t = last[4]; }
+      deposit(at, x, y, t);
+    });
+  }
+  __syncthreads();
+  top = s_top;
+  long long carry = -1;
+  for (int base = 0; base <= top; base += 64) {  // (every lane takes every trip: top is the same on all)
+    const int j = base + lane;
+    const int p = j <= top ? s_prop[j] : -1;
+    long long key = p >= 0 ? ((long long)p << 32) | (long long)j : -1;
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long u = __shfl_up(key, o);
+      if (lane >= o && u > key) key = u;
+    }
+    if (carry > key) key = carry;
+    carry = __shfl(key, 63);
+    if (j <= top && key >= 0) {  // (row 0 proposes tick 0: every tick has an owner)
+      const int src = (int)(key & 0xffffffffll);
+      out[2 * (size_t)j] = s_xy[2 * src]; out[2 * (size_t)j + 1] = s_xy[2 * src + 1];
+    }
+  }
+  if (lane == 0) { head[0] = (int32_t)q0; head[1] = top + 1; }
+}
+
+// replan_team_pick_apart_kernel: replan_team_pick_kernel's sibling for team_separation -- one wavefront per team, the members
+// serial; that kernel stays what it is.  A candidate's score is the tree's own cost or, with use_claims, the one under the
+// claims exactly as there.  Per eligible candidate the lanes stride over its ticks (replan_apart_count) and read, for every
+// earlier winner of the team, that winner's table at the same tick -- contiguous across the lanes, no dependent chain --, one
+// wave sum gives n, and every lane folds the same numbers.  The earlier winners' episodes are a wave-private list in LDS
+// (lane 0 appends, wave_sync orders it for the other lanes).  Through global memory the kernel reads only what an EARLIER launch
+// wrote -- the tables (rrt_course_ticks_kernel), the words, the summaries, the group records (which lane 0 reads and rewrites
+// itself) --, never what another lane of this launch stored: so the L1-cached loads need no acquire / release handling here.
+static __global__ __launch_bounds__(REPLAN_PICK_WAVES * 64) void replan_team_pick_apart_kernel(ReplanPickDev T, ReplanApartDev A) {
+  __shared__ int32_t s_trail[REPLAN_PICK_WAVES][REPLAN_APART_MAX_TEAM];
+  const int t = (int)blockIdx.x * REPLAN_PICK_WAVES + (int)(threadIdx.x >> 6);
+  if (t >= T.n_teams) return;  // (the whole wavefront)
+  const int lane = lane_id();
+  int32_t* trail = s_trail[threadIdx.x >> 6];
+  const int lo = T.team_off[t], hi = T.team_off[t + 1];
+  const double inf = __builtin_inf();
+  const size_t table = 2 * (size_t)A.W;
+  auto table_of = [&](int ep) { return ReplanTicks{A.head[2 * (size_t)ep], A.head[2 * (size_t)ep + 1], A.xy + table * (size_t)ep}; };
+  uint64_t claimed = 0;
+  int n_trail = 0;
+  for (int i = lo; i < hi; i++) {
+    const int m = T.members[i];
+    const int g = T.slot_of[m];
+    if (g < 0 || g >= T.n_slots) continue;  // (not planning in this round; the same on every lane)
+    const uint64_t mask = T.keep[m] & ~claimed;
+    ReplanApartBest b{inf, 0, -1};
+    double cost[4] = {inf, inf, inf, inf};
+    uint64_t vis_w = 0;
+    for (int k = 0; k < T.K; k++) {
+      const int ep = g * T.K + k;
+      const RrtSummary* s = T.summary + ep;
+      const int L = s->best_path_len;
+      if (s->best_leaf < 0 || L < 1) continue;  // (the same on every lane)
+      double sc[4] = {s->best_cost[0], s->best_cost[1], s->best_cost[2], s->best_cost[3]};
+      uint64_t vis = 0;
+      if (A.use_claims) {
+        if (!T.off && (int64_t)L > T.stride) continue;
+        const uint64_t* w = T.words + (T.off ? T.off[ep] : (int64_t)ep * T.stride);
+        const ReplanPickHits hv = replan_pick_hits(w, lane, L, 64, mask);
+        const int hits = wave_sum_i32(hv.hits);
+        vis = wave_or_u64(hv.vis);
+        replan_pick_score(hits, vis, mask, T.w1, T.w2, s->best_cost[3], T.leaf_t[ep], sc);
+      }
+      if (!replan_apart_eligible(sc[0])) continue;
+      const int n = wave_sum_i32(replan_apart_count(table_of(ep), lane, 64, n_trail, [&](int w) { return table_of(trail[w]); }, A.d2));
+      if (replan_apart_fold(b, n, sc[0], k)) {
+        cost[0] = sc[0]; cost[1] = sc[1]; cost[2] = sc[2]; cost[3] = sc[3];
+        vis_w = vis;
+      }
+    }
+    if (lane == 0) {
+      RrtGroupBest r = T.best[g];
+      if (r.status >= 0) r.status = b.k >= 0 ? 0 : 1 /* AUVP_NO_QUALIFYING_LEAF */;
+      r.winner = b.k >= 0 ? g * T.K + b.k : -1;
+      r.path_len = 0;
+      r.length = 0.0;
+      if (b.k >= 0) {
+        const RrtSummary* s = T.summary + (g * T.K + b.k);
+        r.path_len = s->best_path_len;
+        r.length = s->best_length;
+      }
+      r.cost[0] = cost[0]; r.cost[1] = cost[1]; r.cost[2] = cost[2]; r.cost[3] = cost[3];
+      T.best[g] = r;
+      T.claimed[g] = claimed;
+      A.conflicts[g] = b.k >= 0 ? b.n : 0;
+    }
+    if (b.k >= 0 && n_trail < REPLAN_APART_MAX_TEAM) {  // (the host refuses a larger team)
+      if (lane == 0) trail[n_trail] = g * T.K + b.k;
+      n_trail++;
+      wave_sync();
+    }
+    claimed |= vis_w;
+  }
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_ticks_launch(const auvp::RrtBuffers* B, const auvp::ReplanTicksDev* A,
+                                                                                      hipStream_t stream) {
+  if (A->n_episodes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(auvp::rrt_course_ticks_kernel, dim3(A->n_episodes), dim3(64), 0, stream, B ? *B : auvp::RrtBuffers{}, *A);
+  return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_pick_apart_launch(const auvp::ReplanPickDev* T, const auvp::ReplanApartDev* A,
+                                                                                           hipStream_t stream) {
+  if (T->n_teams <= 0) return hipSuccess;
+  const int blocks = (T->n_teams + auvp::REPLAN_PICK_WAVES - 1) / auvp::REPLAN_PICK_WAVES;
+  hipLaunchKernelGGL(auvp::replan_team_pick_apart_kernel, dim3(blocks), dim3(auvp::REPLAN_PICK_WAVES * 64), 0, stream, *T, *A);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A,
                                                                                       hipStream_t stream) {

@@ -280,6 +280,157 @@ def team_pick_claims(labels, keep, active, cands, weights):
     return out
 
 
+MAX_SEPARATION_TICKS = 1024  # (csrc/replan_apart.h: REPLAN_APART_MAX_TICKS, the LDS tables of rrt_course_ticks_kernel)
+MAX_SEPARATION_TEAM = 1024   # (REPLAN_APART_MAX_TEAM: the winner list of replan_team_pick_apart_kernel)
+
+
+def course_ticks(course_t, course_xy, tick, W):
+    """The tick table of a course, rows 0 .. L-1 root -> leaf (row 0: the AUV's committed state): where the AUV is at the
+    instants s * tick, taking it to stay at the last point it reached -- no interpolation.  q_i = ceil(t_i / tick) (one IEEE
+    division and a ceil, in double); s_lo = q_0, s_hi = s_lo + W - 1, s_last = min(s_hi, max of the non-NaN q_i); owner(s) is the
+    LARGEST row index among the rows with q_i <= s (a q_i < s_lo counts as s_lo; a NaN q_i and a q_i > s_hi own nothing, but
+    the latter -- an infinite time included -- extends the table to s_hi).  Returns (s_lo, xy [s_last - s_lo + 1, 2]), xy[j] the
+    position of owner(s_lo + j).  A course without rows, or one whose q_0 is no number inside int32 (replanning_batch refuses
+    a horizon that could give one), has the empty table (0, xy [0,2]): it conflicts with nothing.
+    csrc/replan_apart.h: replan_tick_q / replan_tick_slot / replan_ticks_build."""
+    t = np.asarray(course_t, dtype=np.float64).reshape(-1)
+    xy = np.asarray(course_xy, dtype=np.float64).reshape(-1, 2)
+    W = int(W)
+    if len(t) == 0:
+        return 0, np.zeros((0, 2))
+    with np.errstate(all="ignore"):
+        q = np.ceil(t / np.float64(tick))
+    if not (q[0] == q[0] and -2.0 ** 31 < q[0] < 2.0 ** 31):
+        return 0, np.zeros((0, 2))
+    owner = [-1] * W  # per tick: the largest row that proposes it
+    top = 0
+    for i in range(len(t)):
+        if q[i] != q[i]:
+            continue
+        r = q[i] - q[0]
+        if r <= 0.0:
+            slot = 0
+        elif r > float(W - 1):
+            top = W - 1
+            continue
+        else:
+            slot = int(r)
+        top = max(top, slot)
+        owner[slot] = max(owner[slot], i)
+    out = np.zeros((top + 1, 2))
+    cur = -1
+    for j in range(top + 1):
+        cur = max(cur, owner[j])
+        out[j] = xy[cur]
+    return int(q[0]), out
+
+
+def tick_conflicts(s_lo, xy, trail, d):
+    """the ticks of the table (s_lo, xy) that are in conflict with the trail, a list of tables: some table of the trail covers
+    the tick and dx * dx + dy * dy < d * d there (plain differences, no contraction; a NaN never conflicts).
+    csrc/replan_apart.h: replan_apart_count."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    if len(xy) == 0 or not trail:
+        return 0
+    d2 = np.float64(d) * np.float64(d)
+    hit = np.zeros(len(xy), dtype=bool)
+    for w_lo, w_xy in trail:
+        a, b = max(int(s_lo), int(w_lo)), min(int(s_lo) + len(xy), int(w_lo) + len(w_xy))
+        if a >= b:
+            continue
+        with np.errstate(all="ignore"):
+            dx = xy[a - s_lo:b - s_lo, 0] - w_xy[a - w_lo:b - w_lo, 0]
+            dy = xy[a - s_lo:b - s_lo, 1] - w_xy[a - w_lo:b - w_lo, 1]
+            hit[a - s_lo:b - s_lo] |= dx * dx + dy * dy < d2
+    return int(hit.sum())
+
+
+def team_pick_separated(labels, keep, active, cands, weights, d, claims):
+    """The winner selection of replanning_batch(team_separation=d) for one round -- the definition the device kernels
+    (csrc/replan_apart.h, replan_kernels.hip) match bit for bit.  Arguments as team_pick_claims takes them; every candidate
+    also carries ticks=(s_lo, xy), its course_ticks table (and needs words / leaf_time only with claims).
+
+    Every team of two or more: the trail is empty (and claimed = 0); its members that are in `active`, in ascending AUV index:
+    a candidate's score is its own cost[0] (claims false) or rescore's under keep[m] & ~claimed (claims true: team_pick_claims'
+    score); it is eligible if score < inf; n is tick_conflicts of its table against the trail; the winner is the smallest
+    (n, score), the lowest tree among equals.  The winner's table joins the trail (and, with claims, its vis the claimed mask).
+    Everybody else gets rrt_group_best's fold over cost[0].  Returns what team_pick_claims returns plus conflicts = the
+    winner's n per group (0 without a winner or a teammate); claimed is 0 everywhere without claims."""
+    active = [int(a) for a in active]
+    slot_of = {a: g for g, a in enumerate(active)}
+    inf = float("inf")
+    out = []
+    for g in range(len(active)):  # rrt_group_best_kernel's record
+        best, win, cost = inf, -1, [inf] * 4
+        for k, c in enumerate(cands[g]):
+            if c is not None and float(c["cost"][0]) < best:
+                best, win, cost = float(c["cost"][0]), k, [float(x) for x in c["cost"]]
+        out.append(dict(winner=win, cost=cost, claimed=0, n_with_leaf=sum(c is not None for c in cands[g]), conflicts=0))
+    team_off, members = team_csr(labels)
+    for t in range(len(team_off) - 1):
+        claimed, trail = 0, []
+        for m in members[team_off[t]:team_off[t + 1]]:
+            g = slot_of.get(int(m))
+            if g is None:
+                continue
+            mask = int(keep[int(m)]) & ~claimed
+            best, best_n, win, cost, vis_w = inf, 0, -1, [inf] * 4, 0
+            for k, c in enumerate(cands[g]):
+                if c is None:
+                    continue
+                if claims:
+                    s, vis = rescore(c["words"], mask, c["cost"][3], c["leaf_time"], weights)
+                else:
+                    s, vis = [float(x) for x in c["cost"]], 0
+                if not s[0] < inf:
+                    continue
+                n = tick_conflicts(c["ticks"][0], c["ticks"][1], trail, d)
+                if win < 0 or n < best_n or (n == best_n and s[0] < best):
+                    best, best_n, win, cost, vis_w = s[0], n, k, s, vis
+            out[g].update(winner=win, cost=cost, claimed=claimed, conflicts=best_n if win >= 0 else 0)
+            if win >= 0:
+                trail.append(cands[g][win]["ticks"])
+            claimed |= vis_w
+    return out
+
+
+def separation_args(team_separation, separation_tick, separation_ticks, labels, span):
+    """replanning_batch's team_separation keywords checked without a device: (d, tick, W), or None with the option off.
+    span: plan_time_budget + replan_time_interval, the part of a course a round commits (the default window).  The check of
+    the horizon's end against the tick is replanning_batch's own."""
+    if team_separation is None:
+        return None
+
+    def positive(x):
+        return (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and math.isfinite(float(x))
+                and float(x) > 0.0)
+
+    if labels is None:
+        raise ValueError("team_separation needs teams")
+    if not positive(team_separation):
+        raise ValueError("team_separation must be None or a finite distance > 0, not %r" % (team_separation,))
+    if not positive(separation_tick):
+        raise ValueError("separation_tick must be a finite time > 0, not %r" % (separation_tick,))
+    d, tick = float(team_separation), float(separation_tick)
+    if separation_ticks is None:
+        W = span / tick
+        W = int(math.ceil(W)) if math.isfinite(W) else 0
+    else:
+        try:
+            ok = not isinstance(separation_ticks, (bool, np.bool_)) and int(separation_ticks) == separation_ticks
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("separation_ticks must be None or an integer, not %r" % (separation_ticks,))
+        W = int(separation_ticks)
+    if not 1 <= W <= MAX_SEPARATION_TICKS:
+        raise ValueError("separation_ticks = %d outside 1 .. %d" % (W, MAX_SEPARATION_TICKS))
+    team_off = team_csr(labels)[0]
+    if len(team_off) > 1 and int(np.diff(team_off).max()) > MAX_SEPARATION_TEAM:
+        raise ValueError("team_separation: a team of %d members, more than %d" % (int(np.diff(team_off).max()), MAX_SEPARATION_TEAM))
+    return d, tick, W
+
+
 def first_bucket_commit(course_t, course_xy, t0, max_traj_time, round_span, keep, habitats_xys):
     """One round of replanning's host step (rrt_dubins.py:82-87) on arrays: the points of the course that splitPath
     (:590-602) puts into its first bucket, and removeHabitat (:604-610) applied to the episode's habitat list given as the
@@ -557,7 +708,7 @@ class RRT:
 
     def replanning_batch(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight,
                          max_iter=None, seeds=None, rngs=None, as_arrays=False, trees_per_auv=1, shark_of=None, commit="host",
-                         teams=None, team_pick=None):
+                         teams=None, team_pick=None, team_separation=None, separation_tick=1.0, separation_ticks=None):
         """N replanning() loops -- independent ones unless `teams` is given --, one exploring launch per round over the AUVs still planning (per-episode
         limits: every AUV its own horizon and habitat list, rrt_explore_lim_kernel).  Entry e equals
         replanning(starts[e], list(habitats), ..., seed=seeds[e]); with rngs[e] (a random.Random, taking precedence over
@@ -618,7 +769,29 @@ class RRT:
         word per possible course point, (max_iter + 1 + the batch's path-point capacity) words for each of the N * K trees,
         reserved at the first round and kept by the context (4.3 GiB for 4 096 AUVs x 4 trees at max_iter=2000; about a sixth of
         what the trees' path points take); it grows with max_iter and with N * K, and where the device cannot provide it the
-        round raises AuvpError (a HIP allocation error).  ValueError, before any launch, without teams or for another value."""
+        round raises AuvpError (a HIP allocation error).  ValueError, before any launch, without teams or for another value.
+
+        team_separation=d (metres, a finite float > 0; needs teams; None: the call as described so far) keeps the courses that
+        teammates commit in one round apart.  It is a criterion of its own beside team_pick and works with None and "claims".
+        A course is looked at on the ticks s * separation_tick (seconds, finite > 0) of a window of separation_ticks = W ticks
+        from the AUV's committed state (an int in 1 .. 1024; None: ceil((plan_time_budget + replan_time_interval) /
+        separation_tick), the part a round commits); between two points an AUV is taken to stay at the last point it reached
+        (course_ticks is the definition).  Per round and team of two or more the members that plan are taken in ascending AUV
+        index; n of a candidate is the number of its ticks at which it is closer than d to the winner some earlier member chose
+        in this round (tick_conflicts: dx * dx + dy * dy < d * d); among the candidates whose score is < inf the winner is the
+        smallest (n, score), the lowest tree among equals (team_pick_separated is the definition).  The score is the tree's own
+        cost, or with team_pick="claims" the cost under list & ~claimed, and the claims accumulate as they do without the
+        option.  Where no candidate has a conflict the choice is the one without the option; so are those of the first planning
+        member of a team and of AUVs without a teammate.  Where every candidate conflicts the least conflicting one is
+        committed and nothing is raised: with as_arrays=True round_conflicts [R] (int64) is the committed winner's n.  Works with
+        any trees_per_auv, shark_of and both commit routes (commit="device": rrt_course_ticks_kernel and
+        replan_team_pick_apart_kernel behind the leaf pass, N * K * W * 16 bytes of scratch, and the count rides in the round
+        record); with rngs on commit="host" with one tree, where the one candidate is chosen and only the count is recorded.
+        Limits: only the courses chosen in THIS round are compared -- not the committed log of earlier rounds, so teammates
+        whose rounds start a few seconds apart are not compared over that gap --; positions are sampled, not swept: choose d with
+        the margin that speed x separation_tick calls for.  ValueError, before any launch: without teams, for a d or tick that is
+        not finite and > 0 or is a bool, W outside 1 .. 1024, a horizon whose end / separation_tick reaches 2**31, or a team of
+        more than 1024 members."""
         N = len(starts)
         sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
         labels = None if teams is None else team_labels(teams, N)
@@ -637,8 +810,11 @@ class RRT:
         if commit == "device" and rngs is not None:
             raise ValueError("rngs cannot be combined with commit='device': continuing a generator takes every episode's draw "
                              "count and a state upload per AUV and round -- the host work this option removes; give seeds")
-        horizon_end = list(self.sharkGrid.keys())[-1][1]
         round_span = plan_time_budget + replan_time_interval
+        sep = separation_args(team_separation, separation_tick, separation_ticks, labels, round_span)
+        horizon_end = list(self.sharkGrid.keys())[-1][1]
+        if sep is not None and not float(horizon_end) / sep[1] < 2.0 ** 31:
+            raise ValueError("separation_tick %r: the horizon's end %r is tick 2**31 or later" % (sep[1], horizon_end))
         all_habitats = list(habitats)
         hab = _circles(all_habitats)
         H = len(all_habitats)
@@ -646,7 +822,7 @@ class RRT:
             max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
         if commit == "device":
             return self._replanning_batch_device(starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight,
-                                                 max_iter, seeds, as_arrays, K, sets, labels, team_pick)
+                                                 max_iter, seeds, as_arrays, K, sets, labels, team_pick, sep)
         gens = [None] * N     # rngs[e]: the global stream of a sequential call
         streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
         for e in range(N):
@@ -672,8 +848,12 @@ class RRT:
                 if ttl[e] + last[e][4] > horizon_end:  # stays clipped for the later rounds too (:76-77)
                     ttl[e] = horizon_end - last[e][4]
             mtt = np.array([ttl[e] + last[e][4] for e in act], dtype=np.float64)
-            claimed = [0] * len(act)
-            if team_pick is not None:
+            claimed, conflicts = [0] * len(act), [0] * len(act)
+            if sep is not None:
+                status, best_cost, tree, paths, claimed, conflicts = self._replan_round_pick(
+                    act, K, streams, gens, last, all_habitats, hab, mtt, keep, weight, max_iter, labels, None if sets is None else sets[act],
+                    sep=sep, claims=team_pick is not None)
+            elif team_pick is not None:
                 status, best_cost, tree, paths, claimed = self._replan_round_pick(act, K, streams, gens, last, all_habitats, hab, mtt, keep,
                                                                                   weight, max_iter, labels, None if sets is None else sets[act])
             elif K > 1:
@@ -693,7 +873,7 @@ class RRT:
                 bucket = p[sel]
                 if as_arrays:
                     traj[e].append(bucket)
-                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(best_cost[i]), int(tree[i]), claimed[i]))
+                    rounds[e].append((len(bucket), keep[e], float(mtt[i]), np.array(best_cost[i]), int(tree[i]), claimed[i], conflicts[i]))
                 else:
                     course = self._materialise_course(paths[i], last_obj[e])
                     objs = [course[j] for j in np.flatnonzero(sel)]
@@ -724,6 +904,8 @@ class RRT:
                                 round_tree=np.array([x[4] for x in r], dtype=np.int64), keep=keep[e], cost=costs[e]))
                 if team_pick is not None:
                     res[-1]["round_claimed"] = np.array([x[5] for x in r], dtype=np.uint64)
+                if sep is not None:
+                    res[-1]["round_conflicts"] = np.array([x[6] for x in r], dtype=np.int64)
             else:
                 c = costs[e]
                 res.append([traj[e], {k + 1: [b, hl] for k, (b, hl) in enumerate(rounds[e])},
@@ -749,7 +931,7 @@ class RRT:
         return costs
 
     def _replanning_batch_device(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter,
-                                 seeds, as_arrays, K, sets, labels=None, team_pick=None):
+                                 seeds, as_arrays, K, sets, labels=None, team_pick=None, sep=None):
         """replanning_batch with commit="device": per round one prepare + run, the winners' selection, and rrt_commit_kernel
         (Context.replan_commit; with team labels replan_team_kernel behind it: the records' keep is the team's); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
         drawing each active AUV's K round seeds from its random.Random."""
@@ -769,7 +951,7 @@ class RRT:
         if labels is not None:
             ctx.replan_set_teams(labels)
         # (a fleet without a team of two or more: everybody gets rrt_group_best's record, which is what it runs)
-        pick = team_pick is not None and len(team_csr(labels)[0]) > 1
+        pick = (team_pick is not None or sep is not None) and len(team_csr(labels)[0]) > 1
         self._batch = None  # (rerank follows an exploring_batch only)
         log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
         while True:
@@ -789,7 +971,10 @@ class RRT:
                                   dist_to_end=self.dist_to_end, diff_max=self.diff_max, min_dist=0.5, max_plan_time=float(max_iter),
                                   habitat_keep=np.repeat(keep[act], K), summaries=False,
                                   shark_set=None if sets is None else np.repeat(sets[act], K))
-            best = ctx.replan_team_pick(act, K) if pick else ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
+            if pick and sep is not None:
+                best = ctx.replan_team_pick_apart(act, K, team_pick is not None, *sep)
+            else:
+                best = ctx.replan_team_pick(act, K) if pick else ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
             bad = best["status"] < 0
             if bad.any():
                 i = int(np.argmax(bad))
@@ -803,7 +988,8 @@ class RRT:
             won = rec["winner"] >= 0
             alive[act[~won]] = False  # no qualifying leaf: the sequential call would raise TypeError
             log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won],
-                        rec["claimed"][won] if pick else np.zeros(int(won.sum()), dtype=np.uint64)))
+                        rec["claimed"][won] if pick else np.zeros(int(won.sum()), dtype=np.uint64),
+                        rec["conflicts"][won].astype(np.int64) if pick else np.zeros(int(won.sum()), dtype=np.int64)))
             last[act] = rec["last"]
             keep[act] = rec["keep"]
         if labels is not None:
@@ -823,10 +1009,11 @@ class RRT:
             r_mtt = np.concatenate([x[3] for x in log])[order]
             r_tree = np.concatenate([x[4] for x in log])[order].astype(np.int64)
             r_claimed = np.concatenate([x[5] for x in log])[order].astype(np.uint64)
+            r_conflicts = np.concatenate([x[6] for x in log])[order]
             first = np.searchsorted(auv[order], np.arange(N + 1))
         else:
             r_rec, r_keep, r_mtt, r_tree = np.zeros(0, _lib.REPLAN_RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0, np.int64)
-            r_claimed = np.zeros(0, np.uint64)
+            r_claimed, r_conflicts = np.zeros(0, np.uint64), np.zeros(0, np.int64)
             first = np.zeros(N + 1, dtype=np.int64)
         res = []
         for e in range(N):
@@ -841,6 +1028,8 @@ class RRT:
                                 keep=int(keep[e]), cost=costs[e]))
                 if team_pick is not None:
                     res[-1]["round_claimed"] = r_claimed[a:b].copy()
+                if sep is not None:
+                    res[-1]["round_conflicts"] = r_conflicts[a:b].copy()
                 continue
             # objects: each round's first row is the previous round's last object (the start object in round 1), the rest are
             # new -- what _materialise_course makes of the course on the host route
@@ -896,10 +1085,13 @@ class RRT:
         summ, paths = self._replan_round_summaries(act, 1, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets)
         return summ["status"], summ["best_cost"], np.zeros(len(act), dtype=np.int64), paths
 
-    def _replan_round_pick(self, act, K, streams, gens, last, all_habitats, hab, mtt, keep, weight, max_iter, labels, sets=None):
+    def _replan_round_pick(self, act, K, streams, gens, last, all_habitats, hab, mtt, keep, weight, max_iter, labels, sets=None,
+                           sep=None, claims=True):
         """one round with team_pick="claims" on the host: K trees per active AUV, the round runs with summaries, EVERY candidate's
         course is copied to the host and team_pick_claims chooses.  Returns as _replan_round, tree = the chosen member, the
-        courses the chosen ones', plus the claimed mask every AUV saw."""
+        courses the chosen ones', plus the claimed mask every AUV saw.  With sep = (d, tick, W), team_separation's round:
+        every candidate also gets its tick table, team_pick_separated chooses (under the claims or without them), and the
+        winners' conflict counts are returned as well."""
         summ, paths = self._replan_round_summaries(act, K, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets)
         cands = []
         for g, e in enumerate(act):
@@ -911,14 +1103,19 @@ class RRT:
                     continue
                 p = p.copy()
                 p[0] = last[e]  # (row 0 is the committed state, as in the commit rule)
-                row.append(dict(words=course_habitat_words(p[:, :2], p[:, 4], self._bins, 0, len(self._bins), hab),
-                                cost=[float(x) for x in s["best_cost"]], leaf_time=float(p[-1, 4])))
+                row.append(dict(cost=[float(x) for x in s["best_cost"]], leaf_time=float(p[-1, 4])))
+                if claims:
+                    row[-1]["words"] = course_habitat_words(p[:, :2], p[:, 4], self._bins, 0, len(self._bins), hab)
+                if sep is not None:
+                    row[-1]["ticks"] = course_ticks(p[:, 4], p[:, :2], sep[1], sep[2])
             cands.append(row)
-        picks = team_pick_claims(labels, keep, act, cands, weight)
+        picks = team_pick_claims(labels, keep, act, cands, weight) if sep is None else team_pick_separated(labels, keep, act, cands, weight,
+                                                                                                           sep[0], claims)
         win = [r["winner"] for r in picks]
         status = np.array([_lib.OK if w >= 0 else _lib.NO_QUALIFYING_LEAF for w in win], dtype=np.int32)
-        return (status, np.array([r["cost"] for r in picks], dtype=np.float64).reshape(-1, 4), np.array(win, dtype=np.int64),
-                [paths[g * K + w] if w >= 0 else np.zeros((0, 7)) for g, w in enumerate(win)], [r["claimed"] for r in picks])
+        out = (status, np.array([r["cost"] for r in picks], dtype=np.float64).reshape(-1, 4), np.array(win, dtype=np.int64),
+               [paths[g * K + w] if w >= 0 else np.zeros((0, 7)) for g, w in enumerate(win)], [r["claimed"] for r in picks])
+        return out if sep is None else out + ([r["conflicts"] for r in picks],)
 
     def _replan_round_best_of(self, act, K, streams, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
         """one round with K trees per active AUV: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s members; the winners are

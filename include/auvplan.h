@@ -224,7 +224,9 @@ typedef struct {
   uint64_t keep;       /* the AUV's list after the round; with teams (auvp_replan_set_teams): its team's list after the round */
   uint64_t claimed;    /* after auvp_replan_team_pick: the habitats the AUV's teammates had claimed when its winner was chosen
                         * (0 for an AUV without a teammate, and after auvp_rrt_group_best) */
-  double _reserved;
+  int32_t conflicts;   /* after auvp_replan_team_pick_apart: the ticks at which the committed winner is closer than d to a course
+                        * an earlier teammate chose in this round (0 after the other two selections) */
+  int32_t _reserved;
 } auvp_replan_record; /* 128 bytes */
 /* A fleet's state on the handle: last = start7 [n_auvs,7], keep = keep0 [n_auvs] (keep_is_shared != 0: keep0[0] for everyone),
  * an empty log, zeroed counters.  It survives auvp_rrt_prepare*, auvp_rrt_run, auvp_world_set_habitats and
@@ -284,6 +286,30 @@ int auvp_replan_team_pick_courses(auvp_handle* h, int32_t n_auvs, const int32_t*
                                   const double* courses_xyt, const double* cost4, const double* leaf_t, const double* length,
                                   const int32_t* bin_lo, const int32_t* bin_hi, const double* weights3,
                                   struct auvp_rrt_group_best* out, uint64_t* claimed_out);
+/* The winner selection that keeps the courses teammates commit in one round apart ("team separation", csrc/replan_apart.h), in
+ * place of auvp_rrt_group_best or auvp_replan_team_pick in a round; groups, K and auv_of as there.  Every tree's own best course
+ * is sampled on the ticks s * tick of a window of W ticks from its AUV's committed state -- between two points the AUV stays at
+ * the last one it reached, the largest row among those with ceil(t / tick) <= s owns tick s -- into a tick table in a scratch
+ * buffer (rrt_course_ticks_kernel, one wavefront per episode; n_active * K * W * 16 bytes, kept by the handle).  Then, for every
+ * team of two or more, the members that are part of the round are taken in ascending AUV index: n of a candidate is the number
+ * of its ticks at which it is closer than d (dx*dx + dy*dy < d*d, no contraction) to the winner an earlier member chose in this
+ * call; among the candidates with score < inf the winner is the smallest (n, score), the lowest tree among equals
+ * (replan_team_pick_apart_kernel, one wavefront per team).  The score is the tree's own best_cost[0] (use_claims == 0: no words
+ * are computed and no scratch for them is reserved) or auvp_replan_team_pick's score under keep & ~claimed (use_claims != 0; the
+ * claims accumulate as there).  Where no candidate has a conflict the records are those of auvp_rrt_group_best /
+ * auvp_replan_team_pick.  The commit's records carry `conflicts`, the winner's n (and `claimed`).  State and argument errors as
+ * auvp_replan_team_pick, and AUVP_ERR_ARG for a d or tick that is not finite and > 0, W outside 1 .. 1024, or a team of more
+ * than 1024 members.  A call that fails launches nothing and changes nothing.  The caveat of auvp_replan_team_pick holds. */
+int auvp_replan_team_pick_apart(auvp_handle* h, int32_t n_active, const int32_t* auv_of /* [n_active] */, int32_t K, int32_t use_claims,
+                                double d, double tick, int32_t W, struct auvp_rrt_group_best* out /* [n_active], may be NULL */);
+/* Probe: auvp_replan_team_pick_courses with the kernels of auvp_replan_team_pick_apart on the caller's candidates (row 0 of a
+ * course is taken as given); conflicts_out [n_active] gets each group's winner's n.  Nothing of the fleet is touched. */
+int auvp_replan_team_pick_apart_courses(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
+                                        const int32_t* auv_of, int32_t K, const int64_t* course_off /* [n_active*K+1] */,
+                                        const double* courses_xyt, const double* cost4, const double* leaf_t, const double* length,
+                                        const int32_t* bin_lo, const int32_t* bin_hi, const double* weights3, int32_t use_claims,
+                                        double d, double tick, int32_t W, struct auvp_rrt_group_best* out, uint64_t* claimed_out,
+                                        int32_t* conflicts_out);
 /* Every AUV's whole committed trajectory, in round order: AUV a's rows are row_off[a] .. row_off[a+1]-1 of rows [*,7].  The only
  * bulk copy to the host (one gather launch, one copy of rows * 56 bytes).  rows == NULL: row_off [n_auvs+1] alone, to size the
  * buffer.  AUVP_ERR_STATE without auvp_replan_begin. */

@@ -1,7 +1,7 @@
 """RRT.replanning_batch throughput (profiles/replan_batch_probe.md).
 
     python tools/replan_batch_probe.py [--sizes 256,1024,4096] [--iters 2000] [--seq 4] [--commit host|device] [--runs 1]
-                                        [--teams T] [--trees K] [--team-pick claims]
+                                        [--teams T] [--trees K] [--team-pick claims] [--separation D]
 
 For N AUVs on a G13-style world (synth.make_world(seed=1, n_obstacles=64), the world of tests/golden/g13_replan_a; plan budget
 2, horizon 150 s, replan interval 98 s) and `iters` iterations per round: every round's launch (AUVs still planning, expansions
@@ -16,7 +16,9 @@ one trajectory download.  --runs R: the batch R times after the warm-up, one lin
 only with --commit host).  --teams T: AUVs e with the same e // T share one habitat list (replanning_batch's teams;
 profiles/replan_teams.md); with --commit device the commit kernel's time then covers replan_team_kernel too.  --trees K:
 trees_per_auv.  --team-pick claims: the team-aware winner selection (profiles/replan_team_pick.md); with --commit device
-commit_kernel_ms then also covers rrt_course_words_kernel and replan_team_pick_kernel."""
+commit_kernel_ms then also covers rrt_course_words_kernel and replan_team_pick_kernel.  --separation D: team_separation=D with
+the default tick and window (profiles/replan_team_separation.md); commit_kernel_ms then covers rrt_course_ticks_kernel and
+replan_team_pick_apart_kernel."""
 import argparse
 import json
 import math
@@ -76,6 +78,7 @@ def main():
     ap.add_argument("--teams", type=int, default=0)
     ap.add_argument("--trees", type=int, default=1)
     ap.add_argument("--team-pick", default=None)
+    ap.add_argument("--separation", type=float, default=None)
     a = ap.parse_args()
     budget, length, interval = 2.0, 150.0, 98.0
     w = synth.make_world(seed=1, n_obstacles=64)
@@ -100,6 +103,8 @@ def main():
             tkw["trees_per_auv"] = a.trees
         if a.team_pick:
             tkw["team_pick"] = a.team_pick
+        if a.separation is not None:
+            tkw["team_separation"] = a.separation
         rrt.replanning_batch(starts[:8], habitats, budget, length, interval, [-3, -3, -4], max_iter=a.iters, seeds=seeds[:8],
                              as_arrays=True, commit=a.commit, **({"trees_per_auv": a.trees} if a.trees > 1 else {}))  # warm-up (code objects, buffers)
         for _ in range(a.runs):
@@ -116,7 +121,7 @@ def main():
                 extra = dict(commit_kernel_ms=round(info["commit_ms"], 3), commit_rounds=info["rounds"], rows=info["rows"],
                              bytes_traj=info["bytes_traj"],
                              bytes_per_round=round((info["bytes_to_host"] - info["bytes_traj"]) / max(info["rounds"], 1), 1))
-            print(json.dumps(dict(probe="replanning_batch", commit=a.commit, auvs=N, teams_of=a.teams, trees=a.trees, team_pick=a.team_pick, iters=a.iters, wall_s=round(wall, 3),
+            print(json.dumps(dict(probe="replanning_batch", commit=a.commit, auvs=N, teams_of=a.teams, trees=a.trees, team_pick=a.team_pick, separation=a.separation, iters=a.iters, wall_s=round(wall, 3),
                                   kernel_ms=round(sum(r["ms"] for r in rounds), 3), expansions=exp,
                                   mexp_s_kernel=round(exp / sum(r["ms"] for r in rounds) / 1e3, 1),
                                   mexp_s_wall=round(exp / wall / 1e6, 2), none=sum(r is None for r in res), **extra,
