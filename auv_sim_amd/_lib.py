@@ -139,6 +139,9 @@ def load():
         L.auvp_rrt_set_episode_grids.argtypes = [vp, C.c_int32, _ip]
         L.auvp_rrt_rerank.argtypes = [vp]
         L.auvp_sf_prob_dev.argtypes = [vp, C.POINTER(C.c_void_p), _ip, _ip, _ip]
+    if hasattr(L, "auvp_sf_last_kernel"):  # (likewise: the forecast on large grids)
+        L.auvp_sf_last_kernel.argtypes = [vp]
+        L.auvp_sf_last_kernel.restype = C.c_char_p
     if hasattr(L, "auvp_replan_begin"):  # (likewise: the device commit step of replanning_batch)
         _u64p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
         L.auvp_replan_begin.argtypes = [vp, C.c_int32, _dp, _u64p, C.c_int32]
@@ -194,7 +197,7 @@ def load():
 OPTION_NAMES = ("ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
                 "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
                 "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES",
-                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR", "PRRT_ROWS_GRID")
+                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR", "PRRT_ROWS_GRID", "SF_WIDE_MIN", "SF_WIDE_BLOCK")
 
 
 def _f64(a, shape=None):
@@ -328,6 +331,29 @@ def prrt_choose_launch(E, n_cu=256, O=0, freq=10.0, max_step=300, n_buckets=0, f
                          max_step=int(max_step), flags=int(flags), freq=float(freq), step_mode=int(step_mode), waits=int(bool(waits)),
                          one_wave_only=int(bool(one_wave_only)), rows=-1 if rows is None else int(bool(rows)))
     return _ask_launch("auvp_prrt_choose_launch", q, _PrrtLaunchChoice(), options, PRRT_KINDS)
+
+
+class _SfLaunchQuery(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "cols", "n_cells", "widest_level", "allow_large", "n_options")] + \
+               [("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
+
+
+class _SfLaunchChoice(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "block", "lds")] + [("name", C.c_char_p)]
+
+
+SF_KINDS = ("one-wave", "wide")
+
+
+def forecast_choose_launch(rows, cols, n_cells=0, widest_level=0, allow_large=False, options=None):
+    """the launch the host would choose for a shark-occupancy forecast on a rows x cols grid (auvp_sf_choose_launch; no GPU
+    needed): a dict -- kind (one of SF_KINDS), name, block (threads per workgroup; one workgroup per filter), lds (bytes), status
+    (0; -2 AUVP_ERR_CAPACITY: more grid entries than the entry point takes; -1 AUVP_ERR_ARG: a shape < 1 or a bad SF_WIDE_BLOCK).
+    allow_large: False = auvp_sf_forecast, True = auvp_sf_forecast_large (`SharkForecast.run(large_grids=True)`); n_cells /
+    widest_level: of the list and its schedule (`forecast_plan`), 0 = not known; options: {name: value} of the options set"""
+    q = _SfLaunchQuery(rows=int(rows), cols=int(cols), n_cells=int(n_cells), widest_level=int(widest_level),
+                       allow_large=int(bool(allow_large)))
+    return _ask_launch("auvp_sf_choose_launch", q, _SfLaunchChoice(), options, SF_KINDS)
 
 
 def forecast_plan(rows, cols, cell_rc):
@@ -467,6 +493,10 @@ class Context:
         p, f, t, c = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(self.L.auvp_sf_prob_dev(self.h, C.byref(p), C.byref(f), C.byref(t), C.byref(c)))
         return p.value, f.value, t.value, c.value
+
+    def sf_last_kernel(self):
+        """name of the kernel the last forecast on this context ran (auvp_sf_last_kernel)"""
+        return (self.L.auvp_sf_last_kernel(self.h) or b"").decode()
 
     # ---- RRT.exploring batch ----
     def rrt_explore_batch(self, init, seeds, n_iter, mode="timebin", freq=30, bin_interval=5, v=2,

@@ -1209,6 +1209,7 @@ PrrtState* prrt_of(auvp_handle* h) {
 #include "pf_types.h"
 #include "pf_host.h"
 #include "forecast_kernel.h"
+#include "forecast_wide_kernel.h"
 #include "forecast_host.h"
 #include "compose_host.h"
 #include "gather_host.h"

@@ -1,16 +1,21 @@
-// forecast_host.h -- host side of the shark-occupancy forecast (auvp_sf_*, include/auvplan.h): the level schedule as a
-// handle-less query, and the launch of sf_forecast_kernel (forecast_kernel.h) on a host array of particle coordinates or on
-// the handle's particle-filter batch where it lies in HBM.
-// Included at the end of auvplan.hip, behind pf_host.h (PfState).
+// forecast_host.h -- host side of the shark-occupancy forecast (auvp_sf_*, include/auvplan.h): the level schedule and the
+// launch choice as handle-less queries, and the launch of sf_forecast_kernel (forecast_kernel.h) or sf_wide_kernel
+// (forecast_wide_kernel.h), whichever sf_choose_launch (forecast_launch.h) names, on a host array of particle coordinates or
+// on the handle's particle-filter batch where it lies in HBM.
+// Included at the end of auvplan.hip, behind pf_host.h (PfState) and the two kernel headers.
 #ifndef AUVP_FORECAST_HOST_H
 #define AUVP_FORECAST_HOST_H
+#include "forecast_launch.h"
 #include "forecast_plan.h"
+
+static_assert(auvp::SF_WIDE_LDS_BYTES == auvp::SFW_LDS_BYTES, "forecast_launch.h reports sf_wide_kernel's static LDS");
 
 namespace {
 
 struct SfState {
   DevBuf xy, prior, p_inf, cell_g, sched_g, level_off, grids, prob, counts, status;
   int F = 0, T = 0, C = 0;  // shape of `prob` after the last forecast that completed (F == 0: none)
+  const char* last_kernel = "";  // the kernel that forecast ran (auvp_sf_last_kernel)
 };
 
 SfState* sf_of(auvp_handle* h) {
@@ -21,25 +26,11 @@ SfState* sf_of(auvp_handle* h) {
   return static_cast<SfState*>(h->sf);
 }
 
-}  // namespace
-
-extern "C" {
-
-int auvp_sf_plan(int32_t rows, int32_t cols, const int32_t* cell_rc, int32_t n_cells, int32_t* level, int32_t* order,
-                 int32_t* level_off, int32_t* n_levels) {
-  const auvp::SfPlan p = auvp::sf_plan(rows, cols, cell_rc, n_cells);
-  if (p.status != auvp::SF_PLAN_OK) return AUVP_ERR_ARG;
-  if (n_levels) *n_levels = p.n_levels;
-  if (level) std::copy(p.level.begin(), p.level.end(), level);
-  if (order) std::copy(p.order.begin(), p.order.end(), order);
-  if (level_off) std::copy(p.level_off.begin(), p.level_off.end(), level_off);
-  return AUVP_OK;
-}
-
-int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t cols, double cell_size, const double* cells,
-                     int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles, const double* prior,
-                     int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k, double norm,
-                     int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status) {
+// auvp_sf_forecast / auvp_sf_forecast_large: one implementation, allow_large is the only difference
+int sf_forecast_impl(auvp_handle* h, bool allow_large, const double* box4, int32_t rows, int32_t cols, double cell_size,
+                     const double* cells, int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles,
+                     const double* prior, int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k,
+                     double norm, int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status) {
   if (!h) return AUVP_ERR_ARG;
   if (!box4 || !cells || !prior) return fail(h, AUVP_ERR_ARG, "null argument");
   if (rows < 1 || cols < 1 || n_cells < 1 || n_filters < 1 || n_particles < 1 || n_rounds < 0)
@@ -47,8 +38,14 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   if (method != 1 && method != 2) return fail(h, AUVP_ERR_ARG, "method %d is neither 1 (prediction1) nor 2 (prediction2)", method);
   if (!(cell_size > 0.0) || !std::isfinite(cell_size)) return fail(h, AUVP_ERR_ARG, "cell_size must be finite and > 0");
   if (norm == 0.0 || std::isnan(norm)) return fail(h, AUVP_ERR_ARG, "norm must be a non-zero number");
-  if ((long long)rows * cols > auvp::SF_MAX_GRID)
-    return fail(h, AUVP_ERR_CAPACITY, "%d x %d grid entries > %d (one workgroup's LDS)", rows, cols, auvp::SF_MAX_GRID);
+  // the launch, before anything is allocated (the choice reads neither the list's length nor its levels today: 0 = not known)
+  const auvp::SfLaunch launch = auvp::sf_choose_launch(rows, cols, n_cells, 0, allow_large, h->opt);
+  if (launch.status == auvp::SF_LAUNCH_CAPACITY)
+    return fail(h, AUVP_ERR_CAPACITY, "%d x %d grid entries > %lld (%s)", rows, cols, launch.limit,
+                allow_large ? "auvp_sf_forecast_large's stated limit" : "one workgroup's LDS; auvp_sf_forecast_large takes larger grids");
+  if (launch.status != auvp::SF_LAUNCH_OK)
+    return fail(h, AUVP_ERR_ARG, "option SF_WIDE_BLOCK must be a multiple of 64 in 64 .. 1024");
+  const bool wide = launch.kind == auvp::SF_KERNEL_WIDE;
   const int G = rows * cols, C = n_cells, F = n_filters, N = n_particles, R = n_rounds;
   const double minx = box4[0], miny = box4[1];
   // cellToIndex per cell, then the schedule (which also validates the list)
@@ -75,7 +72,7 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   }
   HIPCHK(h, hipSetDevice(h->device));
   SfState& S = *sf_of(h);
-  S.F = 0;  // (auvp_sf_prob_dev: nothing to hand out until this forecast has completed)
+  S.F = 0; S.last_kernel = "";  // (auvp_sf_prob_dev: nothing to hand out until this forecast has completed)
   auvp::SfDev D{};
   D.F = F; D.N = N; D.rows = rows; D.cols = cols; D.C = C; D.R = R; D.method = method; D.n_levels = plan.n_levels;
   D.prior_shared = prior_is_shared ? 1 : 0;
@@ -104,10 +101,15 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   D.prior = S.prior.as<double>(); D.p_inf = method == 2 ? S.p_inf.as<double>() : nullptr;
   D.cell_g = S.cell_g.as<int32_t>(); D.sched_g = S.sched_g.as<int32_t>(); D.level_off = S.level_off.as<int32_t>();
   D.grids = S.grids.as<double>(); D.prob = S.prob.as<double>(); D.counts = S.counts.as<int32_t>(); D.status = S.status.as<int32_t>();
-  const size_t lds = auvp::sf_lds_bytes(G);
-  HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(auvp::sf_forecast_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(auvp::sf_forecast_kernel, dim3(F), dim3(64), lds, h->stream, D);
+  const size_t lds = (size_t)launch.lds;
+  if (wide) {  // (its LDS is static)
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(auvp::sf_wide_kernel, dim3(F), dim3(launch.block), 0, h->stream, D);
+  } else {
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(auvp::sf_forecast_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(auvp::sf_forecast_kernel, dim3(F), dim3(64), lds, h->stream, D);
+  }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   if (grids) HIPCHK(h, hipMemcpyAsync(grids, S.grids.p, (size_t)F * T * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -117,8 +119,54 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
   HIPCHK(h, hipStreamSynchronize(h->stream));  // (the host vectors go out of scope)
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms; h->last_grid = F; h->last_block = 64; h->last_lds = (int)lds;
-  S.F = F; S.T = (int)T; S.C = C;
+  h->last_ms = ms; h->last_grid = F; h->last_block = launch.block; h->last_lds = (int)lds;
+  S.F = F; S.T = (int)T; S.C = C; S.last_kernel = launch.name;
+  return AUVP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int auvp_sf_plan(int32_t rows, int32_t cols, const int32_t* cell_rc, int32_t n_cells, int32_t* level, int32_t* order,
+                 int32_t* level_off, int32_t* n_levels) {
+  const auvp::SfPlan p = auvp::sf_plan(rows, cols, cell_rc, n_cells);
+  if (p.status != auvp::SF_PLAN_OK) return AUVP_ERR_ARG;
+  if (n_levels) *n_levels = p.n_levels;
+  if (level) std::copy(p.level.begin(), p.level.end(), level);
+  if (order) std::copy(p.order.begin(), p.order.end(), order);
+  if (level_off) std::copy(p.level_off.begin(), p.level_off.end(), level_off);
+  return AUVP_OK;
+}
+
+int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t cols, double cell_size, const double* cells,
+                     int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles, const double* prior,
+                     int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k, double norm,
+                     int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status) {
+  return sf_forecast_impl(h, false, box4, rows, cols, cell_size, cells, n_cells, n_filters, particles_xy, n_particles, prior,
+                          prior_is_shared, method, p_inf, stay_prob, k, norm, n_rounds, grids, prob, counts, status);
+}
+
+int auvp_sf_forecast_large(auvp_handle* h, const double* box4, int32_t rows, int32_t cols, double cell_size, const double* cells,
+                           int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles,
+                           const double* prior, int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob,
+                           double k, double norm, int32_t n_rounds, double* grids, double* prob, int32_t* counts,
+                           int32_t* status) {
+  return sf_forecast_impl(h, true, box4, rows, cols, cell_size, cells, n_cells, n_filters, particles_xy, n_particles, prior,
+                          prior_is_shared, method, p_inf, stay_prob, k, norm, n_rounds, grids, prob, counts, status);
+}
+
+const char* auvp_sf_last_kernel(auvp_handle* h) {
+  const SfState* S = h ? static_cast<const SfState*>(h->sf) : nullptr;
+  return S ? S->last_kernel : "";
+}
+
+int auvp_sf_choose_launch(const auvp_sf_launch_query* q, auvp_sf_launch_choice* c) {
+  OptionView opt;
+  if (!q || !c || !query_options(q->n_options, q->option_names, q->option_values, &opt)) return AUVP_ERR_ARG;
+  const auvp::SfLaunch p = auvp::sf_choose_launch(q->rows, q->cols, q->n_cells, q->widest_level, q->allow_large != 0, opt);
+  *c = auvp_sf_launch_choice{p.status == auvp::SF_LAUNCH_OK ? AUVP_OK : (p.status == auvp::SF_LAUNCH_CAPACITY ? AUVP_ERR_CAPACITY : AUVP_ERR_ARG),
+                             (int32_t)p.kind, p.block, p.lds, p.name};
   return AUVP_OK;
 }
 

@@ -14,7 +14,9 @@ pins to the reference).  Feeding each round's prediction into the next is NEW gr
 docstring intends ("one prediction per time bin of the trajectory") and what its code fails to do -- it stores the pair
 [initial, prediction] under the next key and dies when that pair is fed back in.
 
-Limits, documented: rows x cols <= 4096 (`AUVP_ERR_CAPACITY` above); a cell may be listed once (the reference would visit
+Limits, documented: rows x cols <= 4096 (`AUVP_ERR_CAPACITY` above), or <= 2**22 with `run(large_grids=True)`: above 4096
+entries `sf_wide_kernel` runs, one workgroup per filter with the grids in HBM (the 200 x 200 world of the planners' benchmark
+is a 201 x 201 grid; method 1 then costs one workgroup barrier per level of the list's schedule and round); a cell may be listed once (the reference would visit
 it twice and see neighbours that come later in the list; `AUVP_ERR_ARG` here); a cell outside the grid is `AUVP_ERR_ARG`
 (the reference: IndexError, or a silently wrapped negative index).  The particles are read where `FilterBatch` keeps them in
 HBM (or from an [F, N, 2] host array); the forecast comes back to the host, and goes to a planner in one of two ways: one
@@ -34,15 +36,17 @@ from . import _lib
 
 _dp, _ip = _lib._dp, _lib._ip
 ZERO_TOTAL = 1  # per-filter status: the correction's total is 0 (the reference's ZeroDivisionError)
+MAX_GRID, MAX_GRID_LARGE = 4096, 1 << 22  # rows x cols at most: `run`, and `run(large_grids=True)` (csrc/forecast_launch.h)
 
 
 class Forecast:
-    """what `SharkForecast.run` returns: grids [F, R+1, rows, cols], prob [F, R+1, C] (the same values in cell_list order: the
+    """what `SharkForecast.run` returns: grids [F, R+1, rows, cols] (None with return_grids=False), prob [F, R+1, C] (the same values in cell_list order: the
     planners' layout), counts [F, rows, cols] int32, status [F] (0, or ZERO_TOTAL: that filter's grids are all zeros)"""
 
-    def __init__(self, grids, prob, counts, status, cell_bounds, kernel_ms, ctx=None, serial=None):
+    def __init__(self, grids, prob, counts, status, cell_bounds, kernel_ms, ctx=None, serial=None, kernel=None):
         self.grids, self.prob, self.counts, self.status = grids, prob, counts, status
         self.cell_bounds, self.kernel_ms = cell_bounds, kernel_ms
+        self.kernel = kernel  # "sf_forecast_kernel" or "sf_wide_kernel" (auvp_sf_last_kernel)
         # the context that holds prob's device copy while `serial` is still its latest forecast (RRT.set_shark_grids)
         self.ctx, self.serial = ctx, serial
 
@@ -84,18 +88,22 @@ class SharkForecast:
             self._ctx = _lib.Context(0)
         return self._ctx
 
-    def run(self, filters_or_xy, prior, rounds, method=("ave", 1), hist=None, stay_prob=0.6, k=0.1, norm=1000):
+    def run(self, filters_or_xy, prior, rounds, method=("ave", 1), hist=None, stay_prob=0.6, k=0.1, norm=1000, large_grids=False,
+            return_grids=True):
         """filters_or_xy: a `FilterBatch` (its particles are read on the device) or an [F, N, 2] array of x, y; prior
         [rows, cols] (shared by all filters) or [F, rows, cols]; method = ("ave" | "hist", 1 | 2) as `SharkUpdate.update`
         takes it, `hist` [rows, cols] = P_inf of "hist"; norm: the particle count `correction` divides by (the reference
-        assumes 1000 whatever N is).  Returns a `Forecast`."""
+        assumes 1000 whatever N is).  large_grids: take grids of more than 4096 entries too (`auvp_sf_forecast_large`: up to
+        2**22, on `sf_wide_kernel`; the same results bit for bit).  return_grids=False: `grids` is not copied to the host and
+        `Forecast.grids` is None (F x (R + 1) x rows x cols x 8 bytes; `prob` is what the planners take).  Returns a `Forecast`."""
         kind, which = method
         if kind not in ("ave", "hist") or which not in (1, 2):
             raise ValueError("method must be ('ave' | 'hist', 1 | 2), not %r" % (method,))
         ctx = self._context(filters_or_xy)
         L = ctx.L
-        L.auvp_sf_forecast.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_double, _dp, C.c_int32, C.c_int32, _dp, C.c_int32,
-                                       _dp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, _dp, _dp, _ip, _ip]
+        forecast = L.auvp_sf_forecast_large if large_grids else L.auvp_sf_forecast
+        forecast.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_double, _dp, C.c_int32, C.c_int32, _dp, C.c_int32,
+                             _dp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, _dp, _dp, _ip, _ip]
         rows, cols, n_cells = self.n_row, self.n_col, len(self.cell_bounds)
         if hasattr(filters_or_xy, "ctx"):
             F, N, xy = filters_or_xy.F, filters_or_xy.N, None
@@ -121,17 +129,19 @@ class SharkForecast:
         R = int(rounds)
         box = _lib._f64(self.boundary.bounds, (4,))
         cells = _lib._f64(self.cell_bounds if n_cells else [], (-1, 4))
-        n_grid = max(rows * cols, 1) if rows * cols <= 4096 else 1  # (above the cap the call fails before anything is written)
-        grids = np.zeros((max(F, 1), max(R, 0) + 1, n_grid))
+        # (above the entry point's cap the call fails before anything is written)
+        n_grid = max(rows * cols, 1) if rows * cols <= (MAX_GRID_LARGE if large_grids else MAX_GRID) else 1
+        grids = np.zeros((max(F, 1), max(R, 0) + 1, n_grid)) if return_grids else None
         prob = np.zeros((max(F, 1), max(R, 0) + 1, max(n_cells, 1)))
         counts = np.zeros((max(F, 1), n_grid), dtype=np.int32)
         status = np.zeros(max(F, 1), dtype=np.int32)
-        ctx._chk(L.auvp_sf_forecast(ctx.h, _lib._p(box), rows, cols, float(self.cell_size), _lib._p(cells), n_cells, int(F),
-                                    _lib._p(xy) if xy is not None else None, int(N), _lib._p(pr), shared, int(which),
-                                    _lib._p(p_inf) if p_inf is not None else None, float(stay_prob), float(k), float(norm), R,
-                                    _lib._p(grids), _lib._p(prob), _lib._p(counts, _ip), _lib._p(status, _ip)))
-        self.last = Forecast(grids.reshape(F, R + 1, rows, cols), prob.reshape(F, R + 1, n_cells), counts.reshape(F, rows, cols),
-                             status, self.cell_bounds, ctx.last_kernel_ms(), ctx, getattr(ctx, "sf_serial", 0) + 1)
+        ctx._chk(forecast(ctx.h, _lib._p(box), rows, cols, float(self.cell_size), _lib._p(cells), n_cells, int(F),
+                          _lib._p(xy) if xy is not None else None, int(N), _lib._p(pr), shared, int(which),
+                          _lib._p(p_inf) if p_inf is not None else None, float(stay_prob), float(k), float(norm), R,
+                          _lib._p(grids) if grids is not None else None, _lib._p(prob), _lib._p(counts, _ip), _lib._p(status, _ip)))
+        self.last = Forecast(grids.reshape(F, R + 1, rows, cols) if grids is not None else None, prob.reshape(F, R + 1, n_cells),
+                             counts.reshape(F, rows, cols), status, self.cell_bounds, ctx.last_kernel_ms(), ctx,
+                             getattr(ctx, "sf_serial", 0) + 1, ctx.sf_last_kernel())
         ctx.sf_serial = self.last.serial
         return self.last
 

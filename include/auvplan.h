@@ -576,11 +576,46 @@ int auvp_sf_forecast(auvp_handle* h, const double* box4, int32_t rows, int32_t c
                      int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles, const double* prior,
                      int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob, double k, double norm,
                      int32_t n_rounds, double* grids, double* prob, int32_t* counts, int32_t* status);
+/* The same forecast without the 4 096-entry limit: the same arguments, the same implementation, the same results bit for bit.
+ * Up to 4 096 grid entries it launches the same kernel as auvp_sf_forecast; from 4 097 to 2^22 entries (a stated condition: one
+ * grid of 32 MiB, every index far inside int32) sf_wide_kernel, one workgroup per filter, whose grids live in HBM -- in `grids`
+ * itself: round j's grid is round j + 1's input; method 1 costs one workgroup barrier per level and round (a raster list of an
+ * r x c grid: r + c - 1 levels; a snake list: one per cell).  Above 2^22 entries AUVP_ERR_CAPACITY, before anything is
+ * allocated.  Device memory: n_filters * (n_rounds + 1) * rows * cols * 8 bytes for the grids whether or not `grids` is NULL
+ * (3.6 GB for 1 024 filters x 11 bins of a 201 x 201 grid; a caller that plans from `prob` passes NULL and spares the copy to
+ * the host); an allocation the device cannot provide is AUVP_ERR_HIP.  Options (auvp_set_option): SF_WIDE_MIN, the smallest rows
+ * x cols that takes sf_wide_kernel here (default 4 097; 1: every grid), and SF_WIDE_BLOCK, its threads per workgroup (a multiple
+ * of 64 in 64 .. 1 024, else AUVP_ERR_ARG). */
+int auvp_sf_forecast_large(auvp_handle* h, const double* box4, int32_t rows, int32_t cols, double cell_size, const double* cells,
+                           int32_t n_cells, int32_t n_filters, const double* particles_xy, int32_t n_particles,
+                           const double* prior, int32_t prior_is_shared, int32_t method, const double* p_inf, double stay_prob,
+                           double k, double norm, int32_t n_rounds, double* grids, double* prob, int32_t* counts,
+                           int32_t* status);
+/* name of the kernel the last completed forecast on this handle ran: "sf_forecast_kernel" or "sf_wide_kernel" ("": none) */
+const char* auvp_sf_last_kernel(auvp_handle* h);
+/* Which kernel a forecast would get, at what shape (no device needed; both entry points go through the same rule,
+ * csrc/forecast_launch.h).  n_cells / widest_level: the list's length and the most cells of one level of its schedule
+ * (auvp_sf_plan), 0 = not known -- carried for a finer rule, not read today.  allow_large: 0 = auvp_sf_forecast, 1 =
+ * auvp_sf_forecast_large.  Options as in auvp_rrt_choose_launch. */
+typedef struct {
+  int32_t rows, cols, n_cells, widest_level, allow_large;
+  int32_t n_options;
+  const char* const* option_names;
+  const int64_t* option_values;
+} auvp_sf_launch_query;
+enum { AUVP_SF_ONE_WAVE = 0, AUVP_SF_WIDE };
+typedef struct {
+  int32_t status; /* AUVP_OK; AUVP_ERR_CAPACITY: more grid entries than the entry point takes; AUVP_ERR_ARG: a shape < 1, a bad SF_WIDE_BLOCK */
+  int32_t kind;   /* AUVP_SF_* */
+  int32_t block, lds; /* threads per workgroup (one workgroup per filter); its LDS bytes, static + dynamic */
+  const char* name;   /* what auvp_sf_last_kernel would report */
+} auvp_sf_launch_choice;
+int auvp_sf_choose_launch(const auvp_sf_launch_query* query, auvp_sf_launch_choice* choice);
 /* The device copy of the last forecast's prob [n_filters, n_rounds+1, n_cells], for auvp_world_set_prob_sets(prob_dev) of a
- * planner's handle: the tables go from the forecast to the planner without leaving HBM.  auvp_sf_forecast synchronises its
+ * planner's handle: the tables go from the forecast to the planner without leaving HBM.  auvp_sf_forecast (and _large) synchronises its
  * stream before it returns, so a copy enqueued afterwards on another handle's stream on the same device is ordered behind the
- * forecast.  The pointer is valid until the next auvp_sf_forecast on this handle or its destruction.  AUVP_ERR_STATE without a
- * completed forecast.  Each output may be NULL. */
+ * forecast.  The pointer is valid until the next auvp_sf_forecast / auvp_sf_forecast_large on this handle or its destruction.
+ * AUVP_ERR_STATE without a completed forecast.  Each output may be NULL. */
 int auvp_sf_prob_dev(auvp_handle* h, const void** prob_dev, int32_t* n_filters, int32_t* n_bins, int32_t* n_cells);
 /* The schedule the forecast kernel walks for method 1 (no device needed): cell_rc [n_cells,2] = (row,
  * column) per list position.  level [n_cells]: 0 where no 4-neighbour is earlier in the list, else 1 + the

@@ -11,7 +11,13 @@ times:
               status to the host (ends in a stream synchronise)
 and `host-reps` times the only route the code had before: FilterBatch.particles() (every particle to the host) + counts in
 Python + SharkUpdate.correction + R x SharkUpdate.predictOnAve per filter, on the same inputs (host clock).  The two routes
-must agree bit for bit (asserted).  One JSON line; the table goes to --out."""
+must agree bit for bit (asserted).  One JSON line; the table goes to --out.
+
+    python tools/forecast_probe.py --large --side 201 [--filters-list 1,256,1024] [--rounds 10] [--reps 20] [--host-filters 1]
+                                   --out profiles/shark_forecast_wide.md
+
+the forecast on large grids: sf_wide_kernel at four workgroup sizes beside sf_forecast_kernel where the grid fits it and the
+Python host chain per filter (`large` below); the tables are APPENDED to --out."""
 import argparse
 import copy
 import json
@@ -57,8 +63,87 @@ def cell(v, fmt="%.3f"):
     return (fmt + " (" + fmt + " - " + fmt + ")") % (float(np.median(v)), min(v), max(v))
 
 
+WIDE_BLOCKS = (64, 256, 512, 1024)
+
+
+def large(a):
+    """--large: sf_wide_kernel (SharkForecast.run(large_grids=True, return_grids=False)) on a side x side raster at 64, 256, 512
+    and 1 024 threads per workgroup, for every F of --filters-list; where the grid fits it (side x side <= 4096) also
+    sf_forecast_kernel, and the wide kernel forced there by option SF_WIDE_MIN = 1.  The variants alternate inside every
+    repetition of one run, so that a drift of the machine meets all of them; kernel times are the handle's events.  Beside
+    them the Python host chain's time per filter (SharkUpdate.correction + R x predictOnAve on the same inputs), whose prob must
+    equal every variant's bit for bit (asserted for the filters it runs).  One JSON line per F; the tables are appended to --out."""
+    side, R, N, cs = a.side, a.rounds, a.particles, 10.0
+    half = (side - 1) * cs / 2
+    boundary = Box(-half, -half, half, half)
+    cells = [Box(-half + c * cs, -half + r * cs, -half + (c + 1) * cs, -half + (r + 1) * cs) for r in range(side) for c in range(side)]
+    prior = np.random.default_rng(1).uniform(0.01, 1.0, size=(side, side))   # (shared by the filters: F x side x side is not uploaded)
+    ctx = _lib.Context(0)
+    fits = side * side <= 4096
+    variants = ([("sf_forecast_kernel", None)] if fits else []) + [("sf_wide_kernel", b) for b in WIDE_BLOCKS]
+    su = SharkUpdate(boundary, cs, cells)
+    sf = SharkForecast(boundary, cs, cells, device_context=ctx)
+    assert (sf.n_row, sf.n_col) == (side, side)
+    try:
+        import torch
+        gpu = torch.cuda.get_device_name(0)
+    except Exception:
+        gpu = "device 0"
+    out = ["", "## %d x %d raster (%d levels), %d rounds, %d particles per filter, method (\"ave\", 1)" % (side, side, 2 * side - 1, R, N), "",
+           "`python tools/forecast_probe.py --large --side %d --rounds %d --particles %d --filters-list %s --reps %d --host-filters %d`"
+           % (side, R, N, ",".join(str(f) for f in a.filters_list), a.reps, a.host_filters),
+           "on one %s (gfx950).  Kernel times in ms from the handle's events, warm: median (min - max) of %d runs, the variants"
+           % (gpu, a.reps), "alternating inside every repetition.", "",
+           "| filters | kernel | threads per workgroup | kernel ms |", "|---|---|---|---|"]
+    host_ms = []
+    for F in a.filters_list:
+        xy = np.random.default_rng(100 + F).normal(scale=0.2 * side * cs, size=(F, N, 2))
+        times = {v: [] for v in variants}
+        prob = {}
+        for rep in range(a.reps + 1):  # (the first pass is the warm-up)
+            for v in variants:
+                name, block = v
+                ctx.set_option("SF_WIDE_MIN", 1 if block else None)
+                ctx.set_option("SF_WIDE_BLOCK", block)
+                res = sf.run(xy, prior, R, large_grids=block is not None, return_grids=False)
+                assert res.kernel == name and not res.status.any(), (res.kernel, name)
+                if rep:
+                    times[v].append(res.kernel_ms)
+                else:
+                    prob[v] = res.prob[:a.host_filters].copy()
+        ctx.set_option("SF_WIDE_MIN", None)
+        ctx.set_option("SF_WIDE_BLOCK", None)
+        for f in range(min(a.host_filters, F)):
+            t0 = time.perf_counter()
+            counts = su._blank()
+            for x, y in xy[f].tolist():
+                qx, qy = (x + half) / cs, (y + half) / cs
+                if 0 <= qx < side and 0 <= qy < side:
+                    counts[int(qy)][int(qx)] += 1
+            grids = [su.correction(counts, prior.tolist())]
+            for _ in range(R):
+                grids.append(copy.deepcopy(su.predictOnAve(copy.deepcopy(grids[-1]), False, 1, 0.6, 0.1)[1]))
+            host_ms.append((time.perf_counter() - t0) * 1e3)
+            want = np.array(grids, dtype=np.float64).reshape(R + 1, side * side)   # (raster: list order == grid order)
+            for v in variants:
+                assert np.array_equal(want, prob[v][f], equal_nan=True), ("the host chain and %s @ %s disagree" % v, f)
+        print(json.dumps(dict(large=True, filters=F, particles=N, grid=[side, side], rounds=R, gpu=gpu,
+                              kernel_ms={"%s@%s" % v: [round(x, 4) for x in t] for v, t in times.items()},
+                              host_chain_ms_per_filter=[round(x, 1) for x in host_ms])), flush=True)
+        for v in variants:
+            out.append("| %d | `%s` | %s | %s |" % (F, v[0], v[1] or 64, cell(times[v], "%.4f")))
+    out += ["", "The Python host chain (counts + `SharkUpdate.correction` + %d x `predictOnAve`) on the same machine: %s ms per filter"
+            % (R, cell(host_ms, "%.1f")), "(host clock, %d runs; its prob equals every variant's bit for bit, asserted in the run)." % len(host_ms)]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write("\n".join(out) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--large", action="store_true", help="the sweep of sf_wide_kernel (see large()); appends to --out")
+    ap.add_argument("--filters-list", type=lambda s: [int(x) for x in s.split(",")], default=[1, 256, 1024])
+    ap.add_argument("--host-filters", type=int, default=1)
     ap.add_argument("--filters", type=int, default=512)
     ap.add_argument("--particles", type=int, default=1000)
     ap.add_argument("--side", type=int, default=20)
@@ -67,6 +152,8 @@ def main():
     ap.add_argument("--host-reps", type=int, default=2)
     ap.add_argument("--out", default=os.path.join("profiles", "shark_forecast.md"))
     a = ap.parse_args()
+    if a.large:
+        return large(a)
     F, N, side, R, cs = a.filters, a.particles, a.side, a.rounds, 10.0
     half = (side - 1) * cs / 2
     boundary = Box(-half, -half, half, half)
