@@ -139,6 +139,11 @@ def load():
         L.auvp_rrt_set_episode_grids.argtypes = [vp, C.c_int32, _ip]
         L.auvp_rrt_rerank.argtypes = [vp]
         L.auvp_sf_prob_dev.argtypes = [vp, C.POINTER(C.c_void_p), _ip, _ip, _ip]
+    if hasattr(L, "auvp_world_set_prob_sets_placed"):  # (likewise: the closed tracking loop)
+        L.auvp_world_set_prob_sets_placed.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.auvp_replan_measure.argtypes = [vp, _ip, C.c_int32, _dp, C.POINTER(C.c_void_p)]
+        L.auvp_replan_meas.argtypes = [vp, _ip, _ip, _dp]
+        L.auvp_world_prob_sets_read.argtypes = [vp, _ip, _dp]
     if hasattr(L, "auvp_sf_last_kernel"):  # (likewise: the forecast on large grids)
         L.auvp_sf_last_kernel.argtypes = [vp]
         L.auvp_sf_last_kernel.restype = C.c_char_p
@@ -390,6 +395,13 @@ class Context:
         self.n_prob_sets = 0
         self.n_replan_auvs = 0
         self._world_stamp = 0  # counts set_world / set_habitats: a user that shares the context sees whether its world still stands
+        self.session = None  # the open ReplanSession that owns this context's world, batch and fleet (rrt_dubins.py); None: none
+
+    def _not_in_session(self, what):
+        """RuntimeError while a ReplanSession owns the context and the call does not come from the session itself"""
+        s = self.session
+        if s is not None and not s.inside:
+            raise RuntimeError("%s: a replanning session is open on this context (finish() it first)" % what)
 
     def close(self):
         if getattr(self, "h", None):
@@ -437,6 +449,7 @@ class Context:
         pr = _f64(prob if prob is not None else [])
         if pr.size != len(bn) * len(ce):
             raise ValueError("prob must be [n_bins, n_cells]")
+        self._not_in_session("set_world")
         self._world_stamp += 1
         self._chk(self.L.auvp_world_set(self.h, _p(ob), len(ob), _p(hb), len(hb), _p(pg), len(pg), _p(bn), len(bn),
                                         _p(ce), len(ce), _p(pr)))
@@ -445,6 +458,7 @@ class Context:
 
     def set_habitats(self, habitats):
         hb = _f64(habitats if habitats is not None else [], (-1, 3))
+        self._not_in_session("set_habitats")
         self._world_stamp += 1
         self._chk(self.L.auvp_world_set_habitats(self.h, _p(hb), len(hb)))
         self.world_sizes["H"] = len(hb)
@@ -454,6 +468,7 @@ class Context:
         """auvp_world_set_prob_sets: prob [G, T, C] on the host, or prob_dev = a device pointer to n_sets such tables (copied
         device to device); neither: the sets are cleared.  T and C are the world's."""
         T, Cn = self.world_sizes.get("T", 0), self.world_sizes.get("C", 0)
+        self._not_in_session("set_prob_sets")
         if prob is None and prob_dev is None:
             self._chk(self.L.auvp_world_set_prob_sets(self.h, 0, None, None))
             self.n_prob_sets = 0
@@ -468,6 +483,20 @@ class Context:
             self._chk(self.L.auvp_world_set_prob_sets(self.h, int(n_sets), None, C.c_void_p(prob_dev)))
         self.n_prob_sets = int(n_sets)
 
+    def set_prob_sets_placed(self, prob_dev, n_sets, n_rounds1, first_bin):
+        """auvp_world_set_prob_sets_placed: the sets from a forecast's device copy [n_sets, n_rounds1, C], bin t = forecast round
+        min(max(t - first_bin, 0), n_rounds1 - 1) (sf_place_kernel)"""
+        self._not_in_session("set_prob_sets_placed")
+        self._chk(self.L.auvp_world_set_prob_sets_placed(self.h, C.c_void_p(prob_dev), int(n_sets), int(n_rounds1),
+                                                         int(self.world_sizes.get("C", 0)), int(first_bin)))
+        self.n_prob_sets = int(n_sets)
+
+    def prob_sets(self):
+        """the handle's probability sets [G, T, C] copied back from HBM (auvp_world_prob_sets_read)"""
+        out = np.zeros((self.n_prob_sets, self.world_sizes.get("T", 0), self.world_sizes.get("C", 0)))
+        self._chk(self.L.auvp_world_prob_sets_read(self.h, None, _p(out)))
+        return out
+
     def prob_set_stats(self, n_sets=None):
         """(absmax [G], one_sign [G]) of the handle's probability sets, as the device computed them"""
         n_sets = self.n_prob_sets if n_sets is None else int(n_sets)
@@ -477,6 +506,7 @@ class Context:
 
     def rrt_set_episode_grids(self, set_of):
         """episode e of the prepared batch ranks its leaves against set set_of[e]; None clears the assignment"""
+        self._not_in_session("rrt_set_episode_grids")
         if set_of is None:
             self._chk(self.L.auvp_rrt_set_episode_grids(self.h, 0, None))
             return
@@ -523,6 +553,7 @@ class Context:
         """max_traj_time [E] and / or habitat_keep [E] (bit masks over the world's habitat table): every episode plans with its
         own horizon and habitat list (auvp_rrt_prepare_episodes; the cap is the largest horizon).  Without both: one horizon.
         shark_set [E]: the episode's probability set (rrt_set_episode_grids, on the per-episode-limits route)."""
+        self._not_in_session("rrt_prepare")
         init = _f64(init, (-1, 6))
         E = len(init)
         lim = None
@@ -619,6 +650,7 @@ class Context:
     def replan_begin(self, start7, keep0):
         """a fleet's state on the handle: start7 [N,7] (x, y, theta, v, traj_time_stamp, plan_time_stamp, length), keep0 one
         habitat bit mask or [N]; an empty trajectory log"""
+        self._not_in_session("replan_begin")
         s = _f64(start7, (-1, 7))
         k = np.ascontiguousarray(np.asarray(keep0, dtype=np.uint64).reshape(-1))
         if len(k) not in (1, len(s)):
@@ -717,6 +749,31 @@ class Context:
         self._chk(self.L.auvp_replan_commit(self.h, len(a), _p(a, _ip), float(round_span),
                                             out.ctypes.data_as(C.c_void_p) if records else None))
         return out[:len(a)] if records else None
+
+    def replan_measure(self, shark_of, n_per_shark, shark_xy):
+        """auvp_replan_measure: the fleet's measurements [F, A, 5] of the sharks at shark_xy [F,2] from its committed states,
+        left in HBM.  Returns the table's device pointer (valid until the next call or replan_begin)."""
+        so = np.ascontiguousarray(np.asarray(shark_of, dtype=np.int32).reshape(-1))
+        if len(so) != self.n_replan_auvs:
+            raise ValueError("shark_of has %d entries, the fleet %d AUVs" % (len(so), self.n_replan_auvs))
+        A = int(n_per_shark)
+        if A < 1 or len(so) % A:
+            raise ValueError("%d AUVs are no multiple of %d AUVs per shark" % (len(so), A))
+        F = len(so) // A
+        if so.min() < 0 or so.max() >= F or np.any(np.bincount(so, minlength=F) != A):
+            raise ValueError("every shark 0 .. %d must be tracked by exactly %d AUVs" % (F - 1, A))
+        xy = _f64(shark_xy, (F, 2))
+        ptr = C.c_void_p()
+        self._chk(self.L.auvp_replan_measure(self.h, _p(so, _ip), A, _p(xy), C.byref(ptr)))
+        return ptr.value
+
+    def replan_meas(self):
+        """the last replan_measure's table on the host, [F, A, 5] (auvp_replan_meas)"""
+        f, a = C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.auvp_replan_meas(self.h, C.byref(f), C.byref(a), None))
+        out = np.zeros((f.value, a.value, 5))
+        self._chk(self.L.auvp_replan_meas(self.h, None, None, _p(out)))
+        return out
 
     def replan_traj(self):
         """(row_off [N+1], rows [row_off[N],7]): every AUV's committed trajectory in round order -- the one bulk download"""

@@ -22,6 +22,8 @@ def _bind():
     L.auvp_pf_set_particles.argtypes = [vp, i32, i32, _dp, _ip, _ip, _up, _ip]
     L.auvp_pf_set_rng.argtypes = [vp, _up, _ip]
     L.auvp_pf_run.argtypes = [vp, i32, i32, i32, _dp, _dp, i32]
+    if hasattr(L, "auvp_pf_run_dev_meas"):  # (an earlier build loaded for a comparison has none)
+        L.auvp_pf_run_dev_meas.argtypes = [vp, i32, i32, i32, vp, _dp, i32]
     L.auvp_pf_particles.argtypes = [vp, _dp, _ip]
     L.auvp_pf_estimates.argtypes = [vp, _dp, _dp, _ip]
     L.auvp_pf_status.argtypes = [vp, _ip, _u64p]
@@ -93,6 +95,19 @@ class FilterBatch:
         self.S = int(n_steps or 1)
         self.ctx._chk(self.L.auvp_pf_run(self.ctx.h, self.S, A, int(phases), _lib._p(m) if m is not None else None,
                                          _lib._p(sx) if sx is not None else None, 1 if log else 0))
+        return self
+
+    def run_dev_meas(self, meas_dev, n_auv, shark_xy, phases=UPDATE | WEIGHTS | MEAN, n_steps=1, log=False):
+        """run with meas [S, F, A, 5] already in HBM on this context's device (auvp_pf_run_dev_meas): meas_dev a device pointer
+        whose producer has synchronised its stream (Context.replan_measure), n_auv = A; shark_xy [S, F, 2] from the host"""
+        S = int(n_steps)
+        sx = np.ascontiguousarray(shark_xy, dtype=np.float64).reshape(-1, self.F, 2)
+        if len(sx) != S:
+            raise ValueError("shark_xy must be [S, F, 2]")
+        if not meas_dev or int(n_auv) < 1:
+            raise ValueError("need a device pointer and n_auv >= 1")
+        self.S = S
+        self.ctx._chk(self.L.auvp_pf_run_dev_meas(self.ctx.h, S, int(n_auv), int(phases), C.c_void_p(meas_dev), _lib._p(sx), 1 if log else 0))
         return self
 
     def particles(self):

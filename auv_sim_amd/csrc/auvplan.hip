@@ -30,6 +30,7 @@
 #include "planner_pipe_kernel.h"
 #include "launch_plan.h"  // (behind every kernel header whose LDS plan and limits the choice reads)
 #include "world_tables.h"
+#include "forecast_place.h"
 
 using namespace auvp;
 
@@ -45,6 +46,8 @@ extern "C" hipError_t auvpi_rrt_leaf_grid_launch(const auvp::WorldDev* W, const 
                                                  const auvp::RrtProbSetDev* sets, int grid, int block, int lds, hipStream_t stream);
 extern "C" hipError_t auvpi_prob_set_stats_launch(const double* prob, long long n_per_set, int n_sets, auvp::RrtProbSetDev* sets,
                                                   hipStream_t stream);
+// ... and sf_place_kernel: the sets from a forecast placed at a first bin (forecast_place.h)
+extern "C" hipError_t auvpi_sf_place_launch(const double* src, double* dst, int n_sets, int T, int R1, int C, int first_bin, hipStream_t stream);
 
 #ifdef AUVP_PIPE_DIAG
 extern "C" hipError_t auvpi_astar_sets_diag(const int* cfg8);  // (astar_sets_kernels.hip; the other launchers: astar_host.h)
@@ -863,6 +866,33 @@ int auvp_world_set_prob_sets(auvp_handle* h, int32_t n_sets, const double* prob_
   return AUVP_OK;
 }
 
+int auvp_world_set_prob_sets_placed(auvp_handle* h, const void* prob_dev, int32_t n_sets, int32_t n_rounds1, int32_t n_cells, int32_t first_bin) {
+  if (!h) return AUVP_ERR_ARG;
+  if (!prob_dev || n_sets < 1 || n_rounds1 < 1) return fail(h, AUVP_ERR_ARG, "need prob_dev, n_sets >= 1 and a forecast of >= 1 rounds");
+  if (!h->have_world || h->W.n_bins < 1 || h->W.n_cells < 1)
+    return fail(h, AUVP_ERR_STATE, "probability sets need a world with time bins and cells (auvp_world_set)");
+  if (n_cells != h->W.n_cells) return fail(h, AUVP_ERR_ARG, "the forecast has %d cells, the world %d", n_cells, h->W.n_cells);
+  const int T = h->W.n_bins;
+  const SfPlacePlan plan = placed_round_of_bin(T, n_rounds1 - 1, first_bin);
+  if (plan.status == SF_PLACE_BAD_BIN) return fail(h, AUVP_ERR_ARG, "first_bin %d outside 0 .. %d", first_bin, T - 1);
+  if (plan.status != SF_PLACE_OK) return fail(h, AUVP_ERR_ARG, "bad shape");
+  if ((long long)n_sets * T > 0x7fffffffll) return fail(h, AUVP_ERR_CAPACITY, "%d sets x %d bins: more than 2^31 - 1 rows", n_sets, T);
+  if (plan.identity) return auvp_world_set_prob_sets(h, n_sets, nullptr, prob_dev);  // (the tables as they lie: one copy, no gather)
+  h->sets_version++;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)T * (size_t)n_cells, bytes = (size_t)n_sets * n * sizeof(double);
+  h->n_sets = 0;
+  h->grids = false;  // (an assignment was checked against the sets that go)
+  HIPCHK(h, h->d_sets_prob.reserve(bytes));
+  HIPCHK(h, h->d_sets_rec.reserve((size_t)n_sets * sizeof(RrtProbSetDev)));
+  HIPCHK(h, auvpi_sf_place_launch(static_cast<const double*>(prob_dev), h->d_sets_prob.as<double>(), n_sets, T, n_rounds1, n_cells, first_bin,
+                                  h->stream));
+  HIPCHK(h, auvpi_prob_set_stats_launch(h->d_sets_prob.as<double>(), (long long)n, n_sets, h->d_sets_rec.as<RrtProbSetDev>(), h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->n_sets = n_sets;
+  return AUVP_OK;
+}
+
 int auvp_world_prob_set_stats(auvp_handle* h, double* absmax, int32_t* one_sign) {
   if (!h) return AUVP_ERR_ARG;
   if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle");
@@ -874,6 +904,18 @@ int auvp_world_prob_set_stats(auvp_handle* h, double* absmax, int32_t* one_sign)
     if (absmax) absmax[g] = rec[(size_t)g].absmax;
     if (one_sign) one_sign[g] = rec[(size_t)g].one_sign;
   }
+  return AUVP_OK;
+}
+
+int auvp_world_prob_sets_read(auvp_handle* h, int32_t* n_sets, double* prob) {
+  if (!h) return AUVP_ERR_ARG;
+  if (h->n_sets < 1) return fail(h, AUVP_ERR_STATE, "no probability sets on this handle");
+  if (n_sets) *n_sets = h->n_sets;
+  if (!prob) return AUVP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)h->n_sets * (size_t)h->W.n_bins * (size_t)h->W.n_cells * sizeof(double);
+  HIPCHK(h, hipMemcpyAsync(prob, h->d_sets_prob.p, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return AUVP_OK;
 }
 

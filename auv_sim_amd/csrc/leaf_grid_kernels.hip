@@ -1,6 +1,7 @@
 // leaf_grid_kernels.hip -- the kernels of the probability sets (auvp_world_set_prob_sets, auvp_rrt_set_episode_grids) as a
 // translation unit of their own: rrt_leaf_grid_kernel, the leaf pass of a batch whose episodes each rank their leaves against
-// their own shark-occupancy table, and prob_set_stats_kernel, the two constants of the leaf pass's error bound per table.
+// their own shark-occupancy table, prob_set_stats_kernel, the two constants of the leaf pass's error bound per table, and
+// sf_place_kernel, which fills the sets from a forecast whose rounds start at a later bin than the planner's first.
 //
 // Why its own unit: rrt_leaf_kernel and rrt_leaf_lim_kernel (auvplan.hip) are sensitive to their build context (rows_kernels.hip
 // records 11 % from a scheduling flag alone); a third instance of rrt_leaf_body.h beside them could move their register
@@ -13,6 +14,7 @@
 
 #define AUVP_LEAF_KERNELS_ELSEWHERE 1  // (rrt_leaf_kernel / rrt_leaf_lim_kernel are auvplan.hip's)
 #include "rrt_explore_kernel.h"
+#include "forecast_place.h"
 
 namespace auvp {
 
@@ -66,7 +68,46 @@ static __global__ __launch_bounds__(PROB_STATS_THREADS) void prob_set_stats_kern
   }
 }
 
+// The sets [F][T][C] from a forecast's prob [F][R1][C] (forecast_place.h): one workgroup per row (f, t), which copies the C doubles
+// of forecast round placed_round(t, first_bin, R1 - 1).  Sixteen bytes per lane and trip where the two rows have the same phase
+// against a 16-byte boundary (always with an even C; with an odd C every other row of either side starts on an odd element, so
+// one element is peeled in front and / or left behind); element by element where the phases differ.  Plain vector loads and
+// stores; rows are disjoint.
+constexpr int SF_PLACE_THREADS = 256;
+static __global__ __launch_bounds__(SF_PLACE_THREADS) void sf_place_kernel(const double* __restrict__ src, double* __restrict__ dst, int n_rows,
+                                                                           int T, int R1, int C, int first_bin) {
+  const int row = blockIdx.x;
+  if (row >= n_rows) return;  // (the whole workgroup)
+  const int f = row / T, t = row - f * T;
+  const int r = placed_round(t, first_bin, R1 - 1);
+  const double* s = src + ((size_t)f * (size_t)R1 + (size_t)r) * (size_t)C;
+  double* d = dst + (size_t)row * (size_t)C;
+  const int tid = threadIdx.x;
+  const int ps = (int)(((uintptr_t)s >> 3) & 1), pd = (int)(((uintptr_t)d >> 3) & 1);
+  if (ps != pd) {
+    for (int i = tid; i < C; i += SF_PLACE_THREADS) d[i] = s[i];
+    return;
+  }
+  const int head = pd < C ? pd : C;  // (an odd first element: on its own, the pairs behind it are aligned)
+  const int n2 = (C - head) / 2;
+  const double2* s2 = reinterpret_cast<const double2*>(s + head);
+  double2* d2 = reinterpret_cast<double2*>(d + head);
+  for (int i = tid; i < n2; i += SF_PLACE_THREADS) d2[i] = s2[i];
+  if (tid == 0) {
+    if (head) d[0] = s[0];
+    if (head + 2 * n2 < C) d[C - 1] = s[C - 1];
+  }
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_sf_place_launch(const double* src, double* dst, int n_sets, int T, int R1, int C,
+                                                                                  int first_bin, hipStream_t stream) {
+  if (n_sets <= 0 || T <= 0 || C <= 0) return hipSuccess;
+  hipLaunchKernelGGL(auvp::sf_place_kernel, dim3((unsigned)(n_sets * T)), dim3(auvp::SF_PLACE_THREADS), 0, stream, src, dst, n_sets * T, T, R1, C,
+                     first_bin);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_rrt_leaf_grid_launch(
     const auvp::WorldDev* W, const auvp::RrtParamsDev* P, const auvp::RrtBuffers* B, int n_episodes, int mark_words,

@@ -141,8 +141,13 @@ int auvp_pf_set_rng(auvp_handle* h, const uint32_t* mt, const int32_t* mt_pos) {
   return AUVP_OK;
 }
 
-int auvp_pf_run(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const double* meas, const double* shark_xy,
-                int32_t flags) {
+}  // extern "C"
+
+namespace {
+
+// auvp_pf_run (meas on the host) and auvp_pf_run_dev_meas (meas in HBM on this handle's device: copied device to device)
+int pf_run_impl(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const double* meas, bool meas_on_device,
+                const double* shark_xy, int32_t flags) {
   if (!h) return AUVP_ERR_ARG;
   PfState& P = *pf_of(h);
   if (!P.ready) return fail(h, AUVP_ERR_STATE, "no particle-filter batch");
@@ -153,7 +158,10 @@ int auvp_pf_run(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, 
   const int F = P.F, N = P.N, S = n_steps, A = (phases & auvp::PF_PHASE_WEIGHTS) ? n_auv : 0;
   P.S = S; P.A = A;
   int rc;
-  if (A && (rc = upload(h, P.meas, meas, (size_t)S * F * A * 5))) return rc;
+  if (A && meas_on_device) {
+    HIPCHK(h, P.meas.reserve((size_t)S * F * A * 5 * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(P.meas.p, meas, (size_t)S * F * A * 5 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  } else if (A && (rc = upload(h, P.meas, meas, (size_t)S * F * A * 5))) return rc;
   if ((phases & auvp::PF_PHASE_MEAN) && (rc = upload(h, P.shark, shark_xy, (size_t)S * F * 2))) return rc;
   HIPCHK(h, P.mean.reserve((size_t)S * F * 2 * sizeof(double)));
   HIPCHK(h, P.err.reserve((size_t)S * F * sizeof(double)));
@@ -181,6 +189,20 @@ int auvp_pf_run(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, 
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms; h->last_grid = F; h->last_block = auvpi_pf_threads(); h->last_lds = (int)lds;
   return AUVP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int auvp_pf_run(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const double* meas, const double* shark_xy,
+                int32_t flags) {
+  return pf_run_impl(h, n_steps, n_auv, phases, meas, false, shark_xy, flags);
+}
+
+int auvp_pf_run_dev_meas(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const void* meas_dev, const double* shark_xy,
+                         int32_t flags) {
+  return pf_run_impl(h, n_steps, n_auv, phases, static_cast<const double*>(meas_dev), true, shark_xy, flags);
 }
 
 int auvp_pf_particles(auvp_handle* h, double* out, int32_t* obj) {

@@ -14,7 +14,9 @@
 #include "replan_teams.h"
 #include "replan_pick.h"
 #include "replan_apart.h"
+#include "replan_measure.h"
 
+extern "C" hipError_t auvpi_replan_measure_launch(const auvp::ReplanMeasureDev* M, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_ticks_launch(const auvp::RrtBuffers* B, const auvp::ReplanTicksDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_pick_apart_launch(const auvp::ReplanPickDev* T, const auvp::ReplanApartDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A, hipStream_t stream);
@@ -61,6 +63,9 @@ struct ReplanState {
   // commit copies as it copies the masks
   DevBuf tick_head, tick_xy, conflicts;
   bool pick_apart = false;
+  // auvp_replan_measure: the member table, the sharks' positions and the last table of measurements [meas_F][meas_A][5]
+  DevBuf meas_members, meas_shark, meas;
+  int meas_F = 0, meas_A = 0;              // 0: no measurement since auvp_replan_begin
 };
 
 ReplanState* replan_of(auvp_handle* h) {
@@ -160,7 +165,58 @@ int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, cons
   S.n_teams = 0;  // (the teams were the old fleet's)
   S.max_team = 0;
   S.pick_pending = false;
+  S.meas_F = S.meas_A = 0;
   S.n_auvs = n_auvs;
+  return AUVP_OK;
+}
+
+int auvp_replan_measure(auvp_handle* h, const int32_t* shark_of, int32_t n_per_shark, const double* shark_xy, const void** meas_dev_out) {
+  if (!h) return AUVP_ERR_ARG;
+  ReplanState* Sp = static_cast<ReplanState*>(h->replan);
+  if (!Sp || Sp->n_auvs < 1) return fail(h, AUVP_ERR_STATE, "auvp_replan_begin not called");
+  ReplanState& S = *Sp;
+  if (!shark_of || !shark_xy) return fail(h, AUVP_ERR_ARG, "shark_of / shark_xy is null");
+  const auvp::ReplanMeasurePlan plan = auvp::replan_measure_members(shark_of, S.n_auvs, n_per_shark);
+  if (plan.status == auvp::REPLAN_MEAS_BAD_SHAPE)
+    return fail(h, AUVP_ERR_ARG, "the fleet's %d AUVs are no multiple >= 1 of %d AUVs per shark", S.n_auvs, n_per_shark);
+  if (plan.status == auvp::REPLAN_MEAS_BAD_SHARK)
+    return fail(h, AUVP_ERR_ARG, "AUV %d: shark %d outside [0, %d)", plan.bad, shark_of[plan.bad], S.n_auvs / n_per_shark);
+  if (plan.status != auvp::REPLAN_MEAS_OK) return fail(h, AUVP_ERR_ARG, "shark %d is not tracked by exactly %d AUVs", plan.bad, n_per_shark);
+  HIPCHK(h, hipSetDevice(h->device));
+  S.meas_F = S.meas_A = 0;
+  int rc;
+  if ((rc = upload(h, S.meas_members, plan.members.data(), plan.members.size()))) return rc;
+  if ((rc = upload(h, S.meas_shark, shark_xy, (size_t)plan.F * 2))) return rc;
+  HIPCHK(h, S.meas.reserve(plan.members.size() * auvp::REPLAN_MEAS_ROW * sizeof(double)));
+  auvp::ReplanMeasureDev M{};
+  M.n = (int32_t)plan.members.size(); M.A = n_per_shark;
+  M.members = S.meas_members.as<int32_t>(); M.last = S.last.as<double>(); M.shark_xy = S.meas_shark.as<double>();
+  M.meas = S.meas.as<double>();
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, auvpi_replan_measure_launch(&M, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (the host tables go out of scope; a reader on another handle's stream is ordered behind)
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms; h->last_grid = (M.n + 63) / 64; h->last_block = 64; h->last_lds = 0;
+  S.meas_F = plan.F; S.meas_A = n_per_shark;
+  if (meas_dev_out) *meas_dev_out = S.meas.p;
+  return AUVP_OK;
+}
+
+int auvp_replan_meas(auvp_handle* h, int32_t* n_sharks, int32_t* n_per_shark, double* meas) {
+  if (!h) return AUVP_ERR_ARG;
+  ReplanState* Sp = static_cast<ReplanState*>(h->replan);
+  if (!Sp || Sp->n_auvs < 1 || Sp->meas_F < 1) return fail(h, AUVP_ERR_STATE, "no auvp_replan_measure since auvp_replan_begin");
+  ReplanState& S = *Sp;
+  if (n_sharks) *n_sharks = S.meas_F;
+  if (n_per_shark) *n_per_shark = S.meas_A;
+  if (!meas) return AUVP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)S.meas_F * (size_t)S.meas_A * auvp::REPLAN_MEAS_ROW * sizeof(double);
+  HIPCHK(h, hipMemcpyAsync(meas, S.meas.p, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  S.bytes_to_host += (long long)bytes;
   return AUVP_OK;
 }
 

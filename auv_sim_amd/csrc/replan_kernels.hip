@@ -9,6 +9,7 @@
 //                       in the state array and in the round's records
 //   rrt_course_words_kernel, replan_team_pick_kernel  the team-aware winner selection (replan_pick.h), see below
 //   rrt_course_ticks_kernel, replan_team_pick_apart_kernel  the selection that keeps teammates' courses apart (replan_apart.h)
+//   replan_measure_kernel  the fleet's range / bearing measurements of its sharks from the committed states (replan_measure.h)
 //
 // Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
 #include <hip/hip_runtime.h>
@@ -22,6 +23,8 @@
 #include "replan_pick.h"
 #include "replan_apart.h"
 #include "rrt_course_walk.h"
+#include "replan_measure.h"
+#include "auvp_math_late.h"
 
 namespace auvp {
 
@@ -451,7 +454,34 @@ static __global__ __launch_bounds__(REPLAN_PICK_WAVES * 64) void replan_team_pic
   }
 }
 
+// ---- measurements from the committed states (replan_measure.h) -----------------------------------------------------------------
+//
+// One lane per row (f, a) of meas [F][A][5]: the AUV's x, y, theta from the fleet's state array, the shark's position, and the
+// row's five doubles with plain stores.  members and n come from the host (replan_measure_members: every AUV index inside the
+// fleet).  The square root is pf_step_kernel's (auvp_sqrt_plain); so is the atan2 (auvp_atan2_late), whose value
+// replan_atan2_round then rounds correctly -- the host definition is math.atan2 (replan_measure.h).
+constexpr int REPLAN_MEAS_THREADS = 64;
+static __global__ __launch_bounds__(REPLAN_MEAS_THREADS) void replan_measure_kernel(ReplanMeasureDev M) {
+  const int i = (int)blockIdx.x * REPLAN_MEAS_THREADS + (int)threadIdx.x;
+  if (i >= M.n) return;
+  const int f = i / M.A;
+  const double* last = M.last + (size_t)REPLAN_ROW * (size_t)M.members[i];
+  const double x = last[0], y = last[1], theta = last[2];
+  const double dx = M.shark_xy[2 * (size_t)f] - x, dy = M.shark_xy[2 * (size_t)f + 1] - y;
+  double* o = M.meas + (size_t)REPLAN_MEAS_ROW * (size_t)i;
+  o[0] = x; o[1] = y; o[2] = theta;
+  o[3] = auvp_sqrt_plain(dx * dx + dy * dy);
+  o[4] = replan_atan2_round(dy, dx, auvp_atan2_late(dy, dx)) - theta;
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_measure_launch(const auvp::ReplanMeasureDev* M, hipStream_t stream) {
+  if (M->n <= 0) return hipSuccess;
+  const int blocks = (M->n + auvp::REPLAN_MEAS_THREADS - 1) / auvp::REPLAN_MEAS_THREADS;
+  hipLaunchKernelGGL(auvp::replan_measure_kernel, dim3(blocks), dim3(auvp::REPLAN_MEAS_THREADS), 0, stream, *M);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_ticks_launch(const auvp::RrtBuffers* B, const auvp::ReplanTicksDev* A,
                                                                                       hipStream_t stream) {

@@ -59,32 +59,76 @@ def pack_shark_grid(sharkGrid):
     return bins, cells, prob.reshape(len(keys), len(cell_keys))
 
 
-def put_shark_tables(ctx, own_bins, own_cells, grids):
+def place_forecast(prob, n_bins, first_bin):
+    """a forecast's prob [F, R+1, C] at the planner's absolute bins: [F, n_bins, C] whose bin t is forecast round
+    min(max(t - first_bin, 0), R) (csrc/forecast_place.h: placed_round)"""
+    prob = np.asarray(prob, dtype=np.float64)
+    idx = np.clip(np.arange(int(n_bins)) - int(first_bin), 0, prob.shape[1] - 1)
+    return np.ascontiguousarray(prob[:, idx, :])
+
+
+class PlacedTables:
+    """the host's view of a forecast placed on the device: table g is gathered from the forecast's host copy when somebody asks
+    (the trajectory costs at the end of a replanning call), not on every round of a tracking loop"""
+
+    def __init__(self, prob, n_bins, first_bin):
+        self.prob, self.n_bins, self.first_bin = prob, int(n_bins), int(first_bin)
+        self.shape = (prob.shape[0], self.n_bins, prob.shape[2])
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, g):
+        return place_forecast(self.prob[g][None], self.n_bins, self.first_bin)[0]
+
+    def __array__(self, dtype=None, copy=None):
+        return place_forecast(self.prob, self.n_bins, self.first_bin)
+
+
+def put_shark_tables(ctx, own_bins, own_cells, grids, first_bin=None):
     """set_shark_grids of RRT and astar_fixLenSOG.astar: the tables of `grids` onto ctx's probability sets (Context.set_prob_sets),
     checked against the planner's own bins [T,2] and cells [C,4].  `grids`: a list of sharkGrid dicts with the planner's bin keys
     and cell order, or a sharkForecast.Forecast -- its prob [F, R+1, C] goes device to device while it is still its context's
-    latest forecast on ctx's device, from its host copy otherwise; None or an empty list clears the sets.  ValueError for
-    tables that do not match.  Returns the host copy [G, T, C], None when cleared."""
+    latest forecast on ctx's device, from its host copy otherwise; None or an empty list clears the sets.  first_bin (a Forecast
+    only): None -- R + 1 must be T and the tables are taken as they lie --, or b in 0 .. T-1: bin t reads forecast round
+    min(max(t - b, 0), R), any R (place_forecast; on the device sf_place_kernel; b == 0 with R + 1 == T is the call without it).
+    ValueError for tables that do not match.  Returns the host copy [G, T, C] (a PlacedTables, gathered on demand, for a forecast
+    placed on the device), None when cleared."""
     if grids is None or (isinstance(grids, (list, tuple)) and len(grids) == 0):
+        if first_bin not in (None, 0):
+            raise ValueError("first_bin needs a Forecast")
         ctx.set_prob_sets()
         return None
     T, Cn = len(own_bins), len(own_cells)
     if hasattr(grids, "prob") and hasattr(grids, "cell_bounds"):  # a Forecast
         fc = grids
-        if fc.prob.ndim != 3 or fc.prob.shape[1] != T:
+        if first_bin is not None:
+            if isinstance(first_bin, (bool, np.bool_)) or not isinstance(first_bin, (int, np.integer)):
+                raise ValueError("first_bin must be an integer, not %r" % (first_bin,))
+            if not 0 <= int(first_bin) < T:
+                raise ValueError("first_bin %d outside 0 .. %d" % (int(first_bin), T - 1))
+        if fc.prob.ndim != 3 or (first_bin is None and fc.prob.shape[1] != T) or fc.prob.shape[1] < 1:
             raise ValueError("the forecast has %d time bins (rounds + 1), the planner %d" % (fc.prob.shape[1], T))
         cb = np.array(fc.cell_bounds, dtype=np.float64).reshape(-1, 4)
         if cb.shape != own_cells.shape or not np.array_equal(cb, own_cells):
             raise ValueError("the forecast's cell list is not the planner's")
+        placed = first_bin is not None and not (int(first_bin) == 0 and fc.prob.shape[1] == T)
         src = getattr(fc, "ctx", None)
         if src is not None and src.device == ctx.device and getattr(src, "sf_serial", None) == getattr(fc, "serial", -1):
             ptr, F, Tf, Cf = src.sf_prob_dev()
             if (F, Tf, Cf) != fc.prob.shape:
                 raise ValueError("the forecast's device copy is [%d, %d, %d], not %r" % (F, Tf, Cf, fc.prob.shape))
+            if placed:
+                ctx.set_prob_sets_placed(ptr, F, Tf, int(first_bin))
+                return PlacedTables(fc.prob, T, first_bin)
             ctx.set_prob_sets(n_sets=F, prob_dev=ptr)
-        else:  # (a forecast of another device, or one its context has since replaced: from the host copy)
-            ctx.set_prob_sets(fc.prob)
-        return np.array(fc.prob, dtype=np.float64)
+            return np.array(fc.prob, dtype=np.float64)
+        # (a forecast of another device, or one its context has since replaced: from the host copy)
+        host = place_forecast(fc.prob, T, first_bin) if placed else np.array(fc.prob, dtype=np.float64)
+        ctx.set_prob_sets(host)
+        return host
+    if first_bin not in (None, 0):
+        raise ValueError("first_bin needs a Forecast")
     tabs = []
     for g, grid in enumerate(grids):
         bins, cells, prob = pack_shark_grid(grid)
@@ -473,6 +517,228 @@ class _Init:
             row[0], row[1], row[2], row[4], row[5], row[6])
 
 
+class ReplanSession:
+    """RRT.replanning_batch(commit="device") as a resumable object (RRT.replanning_session).  The fleet's state -- last [N,7],
+    keep [N], the trajectory log -- lives on the planner's context in HBM; the host keeps [N] mirrors from the round records.
+    round() is one iteration of the loop; set_shark_grids() between two rounds swaps the F shark tables and touches nothing
+    else; finish() downloads the trajectories once and closes the session.  While it is open the session owns the planner's
+    context: every other call on the RRT that would prepare a batch, change the world or the tables, or open a second session
+    raises RuntimeError and leaves the session as it was."""
+
+    def __init__(self, rrt, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter, seeds, K, sets,
+                 labels=None, team_pick=None, sep=None):
+        N, H = len(starts), len(all_habitats)
+        if seeds is None or len(seeds) != N or any(s is None for s in seeds):
+            raise ValueError("AUV %d has neither a seed nor a generator"
+                             % (0 if seeds is None or len(seeds) != N else [s is None for s in seeds].index(True)))
+        if getattr(rrt, "_session", None) is not None:
+            raise RuntimeError("replanning_session: a replanning session is open on this RRT (finish() it first)")
+        self.rrt, self.inside, self.closed = rrt, False, False
+        self._starts, self._all_habitats, self._hab = list(starts), all_habitats, hab
+        self._horizon_end, self.round_span, self._weight, self._max_iter = horizon_end, round_span, weight, int(max_iter)
+        self._K, self._sets, self._labels, self._team_pick, self._sep = K, sets, labels, team_pick, sep
+        self._streams = [random.Random(s) for s in seeds]
+        self._last = np.array([[float(m.x), float(m.y), float(m.theta), float(getattr(m, "v", 0.0) or 0.0), float(m.traj_time_stamp),
+                                float(m.plan_time_stamp), float(m.length)] for m in starts], dtype=np.float64).reshape(N, 7)
+        self._keep = np.full(N, (1 << H) - 1, dtype=np.uint64)
+        self._ttl = np.full(N, float(traj_time_length))
+        self._alive = np.ones(N, dtype=bool)
+        ctx = rrt._ctx
+        ctx.set_habitats(hab)  # (the whole list: every episode's own list is its keep mask over this table)
+        ctx.replan_begin(self._last, self._keep)
+        if labels is not None:
+            ctx.replan_set_teams(labels)
+        # (a fleet without a team of two or more: everybody gets rrt_group_best's record, which is what it runs)
+        self._pick = (team_pick is not None or sep is not None) and len(team_csr(labels)[0]) > 1
+        rrt._batch = None  # (rerank follows an exploring_batch only)
+        self._log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
+        self.round_index = 0
+        rrt._session = ctx.session = self
+
+    # ---- views
+    @staticmethod
+    def _view(a):
+        v = a.view()
+        v.flags.writeable = False
+        return v
+
+    @property
+    def last(self):
+        """[N,7] the AUVs' committed states (read-only)"""
+        return self._view(self._last)
+
+    @property
+    def keep(self):
+        """[N] uint64 the AUVs' habitat lists (read-only); with teams the team's list of the member's last round"""
+        return self._view(self._keep)
+
+    def active(self):
+        """indices of the AUVs that would plan in the next round"""
+        return np.flatnonzero(self._alive & (self._last[:, 4] + self.round_span < self._horizon_end))
+
+    def _open(self, what):
+        if self.closed:
+            raise RuntimeError("%s: the session is closed" % what)
+
+    class _Own:
+        def __init__(self, s):
+            self.s = s
+
+        def __enter__(self):
+            self.s.inside = True
+
+        def __exit__(self, *exc):
+            self.s.inside = False
+
+    def set_shark_grids(self, forecast, first_bin=0):
+        """Swap the F shark tables between two rounds (RRT.set_shark_grids; a Forecast is placed at the planner's absolute
+        bins from first_bin on).  The replan state -- last, keep, the log, the seeds' streams -- is not touched; the number of
+        tables must still cover the session's shark_of (ValueError, and the old tables stay)."""
+        self._open("set_shark_grids")
+        rrt = self.rrt
+        if self._sets is not None:
+            n = 0 if forecast is None else (len(forecast.prob) if hasattr(forecast, "prob") else len(forecast))
+            if n <= int(self._sets.max()):
+                raise ValueError("%d tables do not cover the session's shark_of (up to %d)" % (n, int(self._sets.max())))
+        with self._Own(self):
+            rrt._set_prob = put_shark_tables(rrt._ctx, rrt._bins, rrt._cells, forecast, first_bin)
+
+    def round(self):
+        """One round: the active AUVs' round seeds, one exploring launch, the winners (or the team kernels), the commit on the
+        device.  Returns a dict of [A] arrays -- auv (the active indices), last [A,7], keep, winner (the winning tree of the
+        AUV's K, -1: no qualifying leaf; that AUV stops planning), cost [A,4] -- or None once no AUV is active."""
+        self._open("round")
+        act = self.active()
+        if len(act) == 0:
+            return None
+        rrt, ctx, K, sets, sep = self.rrt, self.rrt._ctx, self._K, self._sets, self._sep
+        last, keep, ttl = self._last, self._keep, self._ttl
+        horizon_end, round_span = self._horizon_end, self.round_span
+        with self._Own(self):
+            t_now = last[act, 4]
+            clip = ttl[act] + t_now > horizon_end  # stays clipped for the later rounds too (:76-77)
+            ttl[act[clip]] = horizon_end - t_now[clip]
+            mtt = ttl[act] + t_now
+            short = np.floor(mtt / round_span) < 1  # (first_bucket_commit's ValueError, from the host's numbers, before the launch)
+            if short.any():
+                raise ValueError("max_traj_time %r holds no shark-interval bucket of %r" % (float(mtt[np.argmax(short)]), round_span))
+            seed_arg = np.array([self._streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
+            ctx.rrt_explore_batch(np.repeat(last[act][:, [0, 1, 2, 4, 5, 6]], K, axis=0), seed_arg, self._max_iter, mode="timebin",
+                                  freq=rrt.freq, bin_interval=5, v=2, max_traj_time=np.repeat(mtt, K), weights=self._weight,
+                                  dist_to_end=rrt.dist_to_end, diff_max=rrt.diff_max, min_dist=0.5, max_plan_time=float(self._max_iter),
+                                  habitat_keep=np.repeat(keep[act], K), summaries=False,
+                                  shark_set=None if sets is None else np.repeat(sets[act], K))
+            pick = self._pick
+            if pick and sep is not None:
+                best = ctx.replan_team_pick_apart(act, K, self._team_pick is not None, *sep)
+            else:
+                best = ctx.replan_team_pick(act, K) if pick else ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
+            bad = best["status"] < 0
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise _lib.AuvpError(int(best[i]["status"]), ("a tree of AUV %d failed on the device (status %d)" if K > 1 else
+                                                              "AUV %d failed on the device (status %d)") % (act[i], int(best[i]["status"])))
+            rec = ctx.replan_commit(act, round_span)
+            bad = rec["status"] < 0
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise _lib.AuvpError(int(rec[i]["status"]), "AUV %d: the commit step failed on the device (status %d)" % (act[i], int(rec[i]["status"])))
+            won = rec["winner"] >= 0
+            self._alive[act[~won]] = False  # no qualifying leaf: the sequential call would raise TypeError
+            tree = rec["winner"] - np.arange(len(act)) * K
+            self._log.append((act[won], rec[won], keep[act][won], mtt[won], tree[won],
+                              rec["claimed"][won] if pick else np.zeros(int(won.sum()), dtype=np.uint64),
+                              rec["conflicts"][won].astype(np.int64) if pick else np.zeros(int(won.sum()), dtype=np.int64)))
+            last[act] = rec["last"]
+            keep[act] = rec["keep"]
+            self.round_index += 1
+        return dict(auv=act, last=rec["last"].copy(), keep=rec["keep"].copy(), winner=np.where(won, tree, -1).astype(np.int64),
+                    cost=rec["cost"].reshape(-1, 4).copy())
+
+    def close(self):
+        """give the planner's context back without results (finish() does it itself); harmless on a closed session"""
+        if not self.closed:
+            self.closed = True
+            if self.rrt._session is self:
+                self.rrt._session = None
+            if self.rrt._ctx.session is self:
+                self.rrt._ctx.session = None
+
+    def finish(self, as_arrays=False):
+        """What replanning_batch returns, from the rounds run so far; the session is closed afterwards.  Every trajectory's
+        cost is taken against the shark tables SET LAST (set_shark_grids), not against the tables each round was planned
+        under: with tables that change, the cost describes the trajectory under the latest forecast."""
+        self._open("finish")
+        try:
+            with self._Own(self):
+                return self._results(as_arrays)
+        finally:
+            self.close()
+
+    def _results(self, as_arrays):
+        rrt, ctx, starts, all_habitats, hab = self.rrt, self.rrt._ctx, self._starts, self._all_habitats, self._hab
+        N, H = len(starts), len(all_habitats)
+        labels, team_pick, sep, sets = self._labels, self._team_pick, self._sep, self._sets
+        last, keep, alive, log = self._last, self._keep, self._alive, self._log
+        if labels is not None:
+            # a member that stopped planning holds the team's list of its last round: lists only shrink, so the AND over the
+            # host's copies is the team's final one
+            keep = np.array(team_fold(keep, labels), dtype=np.uint64)
+        row_off, rows_all = ctx.replan_traj()
+        done = [int(e) for e in np.flatnonzero(alive)]
+        rows = {e: rows_all[row_off[e]:row_off[e + 1]] for e in done}
+        costs = rrt._replan_costs(done, rows, last[:, 4], hab, sets)
+        # the rounds of every AUV, in round order: one stable sort of all the rounds' records by AUV
+        if log:
+            auv = np.concatenate([x[0] for x in log])
+            order = np.argsort(auv, kind="stable")
+            r_rec = np.concatenate([x[1] for x in log])[order]
+            r_keep = np.concatenate([x[2] for x in log])[order]
+            r_mtt = np.concatenate([x[3] for x in log])[order]
+            r_tree = np.concatenate([x[4] for x in log])[order].astype(np.int64)
+            r_claimed = np.concatenate([x[5] for x in log])[order].astype(np.uint64)
+            r_conflicts = np.concatenate([x[6] for x in log])[order]
+            first = np.searchsorted(auv[order], np.arange(N + 1))
+        else:
+            r_rec, r_keep, r_mtt, r_tree = np.zeros(0, _lib.REPLAN_RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0, np.int64)
+            r_claimed, r_conflicts = np.zeros(0, np.uint64), np.zeros(0, np.int64)
+            first = np.zeros(N + 1, dtype=np.int64)
+        res = []
+        for e in range(N):
+            if not alive[e]:
+                res.append(None)
+                continue
+            a, b = int(first[e]), int(first[e + 1])
+            lens = r_rec["n_committed"][a:b].astype(np.int64)
+            if as_arrays:
+                res.append(dict(traj=rows[e], round_len=lens, round_keep=r_keep[a:b].copy(), round_max_traj_time=r_mtt[a:b].copy(),
+                                round_cost=r_rec["cost"][a:b].reshape(-1, 4).copy(), round_tree=r_tree[a:b].copy(),
+                                keep=int(keep[e]), cost=costs[e]))
+                if team_pick is not None:
+                    res[-1]["round_claimed"] = r_claimed[a:b].copy()
+                if sep is not None:
+                    res[-1]["round_conflicts"] = r_conflicts[a:b].copy()
+                continue
+            # objects: each round's first row is the previous round's last object (the start object in round 1), the rest are
+            # new -- what _materialise_course makes of the course on the host route
+            traj, rounds, prev, at = [], {}, starts[e], 0
+            for k, n in enumerate(lens):
+                objs = [prev] + [Motion_plan_state(float(r[0]), float(r[1]), theta=float(r[2]), v=float(r[3]), traj_time_stamp=float(r[4]),
+                                                   plan_time_stamp=float(r[5]), length=float(r[6])) for r in rows[e][at + 1:at + n]]
+                if n == 0:
+                    objs = []
+                at += int(n)
+                traj.extend(objs)
+                kb = int(r_keep[a + k])
+                rounds[k + 1] = [objs, [all_habitats[h] for h in range(H) if (kb >> h) & 1]]
+                if objs:
+                    prev = objs[-1]
+            c = costs[e]
+            res.append([traj, rounds, [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
+                        [all_habitats[h] for h in range(H) if (int(keep[e]) >> h) & 1]])
+        return res
+
+
 class RRT:
     """Goal-less cost-optimising RRT with random-arc steering (reference class of the same name)."""
 
@@ -500,18 +766,28 @@ class RRT:
         self._mps_cache = None
         self._set_prob = None   # host copy [G, T, C] of the shark tables of set_shark_grids (None: none)
         self._batch = None      # what rerank needs of the last exploring_batch: (initials, shark_interval, max_traj_time)
+        self._session = None    # the open ReplanSession (replanning_session), None: none
 
     @property
     def n_shark_sets(self):
         return 0 if self._set_prob is None else len(self._set_prob)
 
-    def set_shark_grids(self, grids):
+    def set_shark_grids(self, grids, first_bin=None):
         """One shark-occupancy table per tracked shark, for shark_of: a list of sharkGrid dicts with the constructor's bin
         keys and cell order, or a sharkForecast.Forecast -- then its prob [F, R+1, C] goes from the forecast's context to
-        the planner's without leaving HBM (R + 1 must be the planner's bin count and the cell list the planner's).  ValueError
-        otherwise.  None or an empty list clears the tables.  The constructor's own grid stays the table of every call
-        without shark_of."""
-        self._set_prob = put_shark_tables(self._ctx, self._bins, self._cells, grids)
+        the planner's without leaving HBM (the cell list must be the planner's).  first_bin=None: R + 1 must be the planner's
+        bin count T and round j is bin j.  first_bin=b (0 .. T-1; a Forecast only): the forecast speaks from "now" and now is
+        bin b -- set f's bin t reads forecast round min(max(t - b, 0), R), for any R; unless b == 0 and R + 1 == T (the call
+        without first_bin) sf_place_kernel gathers the rows on the device.  ValueError otherwise.  None or an empty list
+        clears the tables.  The constructor's own grid stays the table of every call without shark_of.  RuntimeError while a
+        replanning session is open: its own set_shark_grids is the way then."""
+        self._no_session("set_shark_grids")
+        self._set_prob = put_shark_tables(self._ctx, self._bins, self._cells, grids, first_bin)
+
+    def _no_session(self, what):
+        session = getattr(self, "_session", None)
+        if session is not None and not session.inside:
+            raise RuntimeError("%s: a replanning session is open on this RRT (finish() it first)" % what)
 
     # ------------------------------------------------------------------ reference API
     def exploring(self, initial, habitats, plot_interval, bin_interval, v, shark_interval, traj_time_stamp=False,
@@ -538,6 +814,7 @@ class RRT:
         Per-episode limits (time-bin mode): max_traj_time [E] gives every episode its own horizon, habitat_masks ([E] ints,
         bit h = habitats[h], or [E, H] booleans) its own habitat list -- the subsequence of `habitats` its mask selects.
         Episode e then equals exploring(initials[e], [its habitats], ..., max_traj_time=max_traj_time[e])."""
+        self._no_session("exploring_batch")
         E = len(initials)
         sets = None if shark_of is None else shark_set_indices(shark_of, E, self.n_shark_sets, bool(plan_time and traj_time_stamp))
         if max_iter is None:
@@ -564,6 +841,7 @@ class RRT:
         grid): what exploring_batch would return with that shark_of, for the price of the leaf pass -- no tree is grown.  The
         batch must have gone the per-episode-limits route (shark_of, habitat_masks or max_traj_time [E]) for a table per
         episode; AuvpError (AUVP_ERR_STATE) otherwise, or without a batch."""
+        self._no_session("rerank")
         if self._batch is None:
             raise _lib.AuvpError(-4, "no exploring_batch to rank again")
         sets = None if shark_of is None else shark_set_indices(shark_of, len(self._batch[0]), self.n_shark_sets)
@@ -626,6 +904,7 @@ class RRT:
         the host and turned into objects.  Returns N dicts shaped like exploring's plus "tree", the winning member's index;
         None where no member has a qualifying leaf.  A member that failed on the device raises AuvpError.
         shark_of [N]: AUV i's K trees are all ranked against table shark_of[i] of set_shark_grids."""
+        self._no_session("exploring_best_of")
         N = len(initials)
         if seeds is None or len(seeds) != N or N == 0:
             raise ValueError("seeds [N][K] are required: one row of K seeds per AUV")
@@ -681,6 +960,7 @@ class RRT:
         boundary stay on the device for later exploring() / check_collision() calls."""
         from .cost import habitat_shark_cost_func
         from .sharkEstimate import SharkUpdate
+        self._no_session("replanning")
         self.sharkEstimate = SharkUpdate(self.boundary_poly, 10, self.cell_list)
         horizon_end = list(self.sharkGrid.keys())[-1][1]
         round_span = plan_time_budget + replan_time_interval  # also the shark_interval handed to exploring (:80)
@@ -733,8 +1013,8 @@ class RRT:
 
         commit="device": the step between two rounds runs on the device (rrt_commit_kernel behind the winners' selection) --
         the courses stay in HBM, one 128-byte record per AUV and round comes back, the host's part of a round is numpy over
-        [N] arrays, and the committed trajectories are downloaded once at the end.  The results equal commit="host" (the
-        default) in every field.  Seeds only (rngs raises ValueError); the ValueError for a horizon that holds no whole bucket
+        [N] arrays, and the committed trajectories are downloaded once at the end (a ReplanSession, run to its end:
+        replanning_session gives the same loop one round at a time).  The results equal commit="host" (the default) in every field.  Seeds only (rngs raises ValueError); the ValueError for a horizon that holds no whole bucket
         is raised before the round is launched.
 
         teams [N] integers: AUVs with the same label >= 0 form a team that shares one habitat list, a label < 0 is an AUV on
@@ -792,37 +1072,21 @@ class RRT:
         the margin that speed x separation_tick calls for.  ValueError, before any launch: without teams, for a d or tick that is
         not finite and > 0 or is a bool, W outside 1 .. 1024, a horizon whose end / separation_tick reaches 2**31, or a team of
         more than 1024 members."""
-        N = len(starts)
-        sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
-        labels = None if teams is None else team_labels(teams, N)
-        if team_pick is not None:
-            if team_pick != "claims":
-                raise ValueError("team_pick must be None or 'claims', not %r" % (team_pick,))
-            if labels is None:
-                raise ValueError("team_pick='claims' needs teams")
-        K = int(trees_per_auv)
-        if K < 1:
-            raise ValueError("trees_per_auv must be >= 1")
-        if K > 1 and rngs is not None:
-            raise ValueError("rngs cannot be combined with trees_per_auv > 1: one generator cannot continue K streams")
-        if commit not in ("host", "device"):
-            raise ValueError("commit must be 'host' or 'device', not %r" % (commit,))
-        if commit == "device" and rngs is not None:
-            raise ValueError("rngs cannot be combined with commit='device': continuing a generator takes every episode's draw "
-                             "count and a state upload per AUV and round -- the host work this option removes; give seeds")
-        round_span = plan_time_budget + replan_time_interval
-        sep = separation_args(team_separation, separation_tick, separation_ticks, labels, round_span)
-        horizon_end = list(self.sharkGrid.keys())[-1][1]
-        if sep is not None and not float(horizon_end) / sep[1] < 2.0 ** 31:
-            raise ValueError("separation_tick %r: the horizon's end %r is tick 2**31 or later" % (sep[1], horizon_end))
-        all_habitats = list(habitats)
-        hab = _circles(all_habitats)
+        self._no_session("replanning_batch")
+        N, sets, labels, K, round_span, sep, horizon_end, all_habitats, hab, max_iter = self._replan_args(
+            starts, habitats, plan_time_budget, replan_time_interval, max_iter, trees_per_auv, shark_of, teams, team_pick,
+            team_separation, separation_tick, separation_ticks, rngs, commit)
         H = len(all_habitats)
-        if max_iter is None:
-            max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
         if commit == "device":
-            return self._replanning_batch_device(starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight,
-                                                 max_iter, seeds, as_arrays, K, sets, labels, team_pick, sep)
+            # the one copy of the device loop: a session, its rounds until nobody plans any more, its end
+            session = ReplanSession(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter, seeds,
+                                    K, sets, labels, team_pick, sep)
+            try:
+                while session.round() is not None:
+                    pass
+                return session.finish(as_arrays)
+            finally:
+                session.close()
         gens = [None] * N     # rngs[e]: the global stream of a sequential call
         streams = [None] * N  # seeds[e]: replanning's private stream, one 63-bit seed per round
         for e in range(N):
@@ -930,125 +1194,53 @@ class RRT:
                 costs.update({e: out[i] for i, e in enumerate(grp)})
         return costs
 
-    def _replanning_batch_device(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter,
-                                 seeds, as_arrays, K, sets, labels=None, team_pick=None, sep=None):
-        """replanning_batch with commit="device": per round one prepare + run, the winners' selection, and rrt_commit_kernel
-        (Context.replan_commit; with team labels replan_team_kernel behind it: the records' keep is the team's); the host sees [A] records and works on [N] arrays.  The only per-AUV Python of a round is
-        drawing each active AUV's K round seeds from its random.Random."""
-        N, H = len(starts), len(all_habitats)
-        if seeds is None or len(seeds) != N or any(s is None for s in seeds):
-            raise ValueError("AUV %d has neither a seed nor a generator"
-                             % (0 if seeds is None or len(seeds) != N else [s is None for s in seeds].index(True)))
-        streams = [random.Random(s) for s in seeds]
-        last = np.array([[float(m.x), float(m.y), float(m.theta), float(getattr(m, "v", 0.0) or 0.0), float(m.traj_time_stamp),
-                          float(m.plan_time_stamp), float(m.length)] for m in starts], dtype=np.float64).reshape(N, 7)
-        keep = np.full(N, (1 << H) - 1, dtype=np.uint64)
-        ttl = np.full(N, float(traj_time_length))
-        alive = np.ones(N, dtype=bool)
-        ctx = self._ctx
-        ctx.set_habitats(hab)  # (the whole list: every episode's own list is its keep mask over this table)
-        ctx.replan_begin(last, keep)
-        if labels is not None:
-            ctx.replan_set_teams(labels)
-        # (a fleet without a team of two or more: everybody gets rrt_group_best's record, which is what it runs)
-        pick = (team_pick is not None or sep is not None) and len(team_csr(labels)[0]) > 1
-        self._batch = None  # (rerank follows an exploring_batch only)
-        log = []  # per round: (AUVs that committed, their records, keep and max_traj_time at that round, winning member)
-        while True:
-            act = np.flatnonzero(alive & (last[:, 4] + round_span < horizon_end))
-            if len(act) == 0:
-                break
-            t_now = last[act, 4]
-            clip = ttl[act] + t_now > horizon_end  # stays clipped for the later rounds too (:76-77)
-            ttl[act[clip]] = horizon_end - t_now[clip]
-            mtt = ttl[act] + t_now
-            short = np.floor(mtt / round_span) < 1  # (first_bucket_commit's ValueError, from the host's numbers, before the launch)
-            if short.any():
-                raise ValueError("max_traj_time %r holds no shark-interval bucket of %r" % (float(mtt[np.argmax(short)]), round_span))
-            seed_arg = np.array([streams[e].getrandbits(63) for e in act for _ in range(K)], dtype=np.uint64)
-            ctx.rrt_explore_batch(np.repeat(last[act][:, [0, 1, 2, 4, 5, 6]], K, axis=0), seed_arg, int(max_iter), mode="timebin",
-                                  freq=self.freq, bin_interval=5, v=2, max_traj_time=np.repeat(mtt, K), weights=weight,
-                                  dist_to_end=self.dist_to_end, diff_max=self.diff_max, min_dist=0.5, max_plan_time=float(max_iter),
-                                  habitat_keep=np.repeat(keep[act], K), summaries=False,
-                                  shark_set=None if sets is None else np.repeat(sets[act], K))
-            if pick and sep is not None:
-                best = ctx.replan_team_pick_apart(act, K, team_pick is not None, *sep)
-            else:
-                best = ctx.replan_team_pick(act, K) if pick else ctx.rrt_group_best(np.arange(len(act) + 1, dtype=np.int64) * K)
-            bad = best["status"] < 0
-            if bad.any():
-                i = int(np.argmax(bad))
-                raise _lib.AuvpError(int(best[i]["status"]), ("a tree of AUV %d failed on the device (status %d)" if K > 1 else
-                                                              "AUV %d failed on the device (status %d)") % (act[i], int(best[i]["status"])))
-            rec = ctx.replan_commit(act, round_span)
-            bad = rec["status"] < 0
-            if bad.any():
-                i = int(np.argmax(bad))
-                raise _lib.AuvpError(int(rec[i]["status"]), "AUV %d: the commit step failed on the device (status %d)" % (act[i], int(rec[i]["status"])))
-            won = rec["winner"] >= 0
-            alive[act[~won]] = False  # no qualifying leaf: the sequential call would raise TypeError
-            log.append((act[won], rec[won], keep[act][won], mtt[won], (rec["winner"] - np.arange(len(act)) * K)[won],
-                        rec["claimed"][won] if pick else np.zeros(int(won.sum()), dtype=np.uint64),
-                        rec["conflicts"][won].astype(np.int64) if pick else np.zeros(int(won.sum()), dtype=np.int64)))
-            last[act] = rec["last"]
-            keep[act] = rec["keep"]
-        if labels is not None:
-            # a member that stopped planning holds the team's list of its last round: lists only shrink, so the AND over the
-            # host's copies is the team's final one
-            keep = np.array(team_fold(keep, labels), dtype=np.uint64)
-        row_off, rows_all = ctx.replan_traj()
-        done = [int(e) for e in np.flatnonzero(alive)]
-        rows = {e: rows_all[row_off[e]:row_off[e + 1]] for e in done}
-        costs = self._replan_costs(done, rows, last[:, 4], hab, sets)
-        # the rounds of every AUV, in round order: one stable sort of all the rounds' records by AUV
-        if log:
-            auv = np.concatenate([x[0] for x in log])
-            order = np.argsort(auv, kind="stable")
-            r_rec = np.concatenate([x[1] for x in log])[order]
-            r_keep = np.concatenate([x[2] for x in log])[order]
-            r_mtt = np.concatenate([x[3] for x in log])[order]
-            r_tree = np.concatenate([x[4] for x in log])[order].astype(np.int64)
-            r_claimed = np.concatenate([x[5] for x in log])[order].astype(np.uint64)
-            r_conflicts = np.concatenate([x[6] for x in log])[order]
-            first = np.searchsorted(auv[order], np.arange(N + 1))
-        else:
-            r_rec, r_keep, r_mtt, r_tree = np.zeros(0, _lib.REPLAN_RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0), np.zeros(0, np.int64)
-            r_claimed, r_conflicts = np.zeros(0, np.uint64), np.zeros(0, np.int64)
-            first = np.zeros(N + 1, dtype=np.int64)
-        res = []
-        for e in range(N):
-            if not alive[e]:
-                res.append(None)
-                continue
-            a, b = int(first[e]), int(first[e + 1])
-            lens = r_rec["n_committed"][a:b].astype(np.int64)
-            if as_arrays:
-                res.append(dict(traj=rows[e], round_len=lens, round_keep=r_keep[a:b].copy(), round_max_traj_time=r_mtt[a:b].copy(),
-                                round_cost=r_rec["cost"][a:b].reshape(-1, 4).copy(), round_tree=r_tree[a:b].copy(),
-                                keep=int(keep[e]), cost=costs[e]))
-                if team_pick is not None:
-                    res[-1]["round_claimed"] = r_claimed[a:b].copy()
-                if sep is not None:
-                    res[-1]["round_conflicts"] = r_conflicts[a:b].copy()
-                continue
-            # objects: each round's first row is the previous round's last object (the start object in round 1), the rest are
-            # new -- what _materialise_course makes of the course on the host route
-            traj, rounds, prev, at = [], {}, starts[e], 0
-            for k, n in enumerate(lens):
-                objs = [prev] + [Motion_plan_state(float(r[0]), float(r[1]), theta=float(r[2]), v=float(r[3]), traj_time_stamp=float(r[4]),
-                                                   plan_time_stamp=float(r[5]), length=float(r[6])) for r in rows[e][at + 1:at + n]]
-                if n == 0:
-                    objs = []
-                at += int(n)
-                traj.extend(objs)
-                kb = int(r_keep[a + k])
-                rounds[k + 1] = [objs, [all_habitats[h] for h in range(H) if (kb >> h) & 1]]
-                if objs:
-                    prev = objs[-1]
-            c = costs[e]
-            res.append([traj, rounds, [float(c[0]), [float(c[1]), float(c[2]), float(c[3])]],
-                        [all_habitats[h] for h in range(H) if (int(keep[e]) >> h) & 1]])
-        return res
+    def _replan_args(self, starts, habitats, plan_time_budget, replan_time_interval, max_iter, trees_per_auv, shark_of, teams, team_pick,
+                     team_separation, separation_tick, separation_ticks, rngs=None, commit="device"):
+        """the argument checks replanning_batch and replanning_session share, in one order, before any launch"""
+        N = len(starts)
+        sets = None if shark_of is None else shark_set_indices(shark_of, N, self.n_shark_sets)
+        labels = None if teams is None else team_labels(teams, N)
+        if team_pick is not None:
+            if team_pick != "claims":
+                raise ValueError("team_pick must be None or 'claims', not %r" % (team_pick,))
+            if labels is None:
+                raise ValueError("team_pick='claims' needs teams")
+        K = int(trees_per_auv)
+        if K < 1:
+            raise ValueError("trees_per_auv must be >= 1")
+        if K > 1 and rngs is not None:
+            raise ValueError("rngs cannot be combined with trees_per_auv > 1: one generator cannot continue K streams")
+        if commit not in ("host", "device"):
+            raise ValueError("commit must be 'host' or 'device', not %r" % (commit,))
+        if commit == "device" and rngs is not None:
+            raise ValueError("rngs cannot be combined with commit='device': continuing a generator takes every episode's draw "
+                             "count and a state upload per AUV and round -- the host work this option removes; give seeds")
+        round_span = plan_time_budget + replan_time_interval
+        sep = separation_args(team_separation, separation_tick, separation_ticks, labels, round_span)
+        horizon_end = list(self.sharkGrid.keys())[-1][1]
+        if sep is not None and not float(horizon_end) / sep[1] < 2.0 ** 31:
+            raise ValueError("separation_tick %r: the horizon's end %r is tick 2**31 or later" % (sep[1], horizon_end))
+        all_habitats = list(habitats)
+        hab = _circles(all_habitats)
+        if max_iter is None:
+            max_iter = max(1, int(math.ceil(plan_time_budget * self.iters_per_second)))
+        return N, sets, labels, K, round_span, sep, horizon_end, all_habitats, hab, max_iter
+
+    def replanning_session(self, starts, habitats, plan_time_budget, traj_time_length, replan_time_interval, weight, max_iter=None,
+                           seeds=None, trees_per_auv=1, shark_of=None, teams=None, team_pick=None, team_separation=None,
+                           separation_tick=1.0, separation_ticks=None):
+        """replanning_batch(commit="device") one round at a time: a ReplanSession whose round() is one iteration of that call's
+        loop and whose finish() returns what the call returns; between two rounds set_shark_grids may swap the shark tables.
+        The arguments are replanning_batch's (seeds only), with the same ValueErrors before any launch.  RuntimeError while
+        another session is open on this RRT."""
+        self._no_session("replanning_session")
+        if getattr(self, "_session", None) is not None:
+            raise RuntimeError("replanning_session: a replanning session is open on this RRT (finish() it first)")
+        N, sets, labels, K, round_span, sep, horizon_end, all_habitats, hab, max_iter = self._replan_args(
+            starts, habitats, plan_time_budget, replan_time_interval, max_iter, trees_per_auv, shark_of, teams, team_pick,
+            team_separation, separation_tick, separation_ticks)
+        return ReplanSession(self, starts, all_habitats, hab, horizon_end, round_span, traj_time_length, weight, max_iter, seeds, K,
+                             sets, labels, team_pick, sep)
 
     def _replan_round_summaries(self, act, K, streams, gens, last, all_habitats, mtt, keep, weight, max_iter, sets=None):
         """K trees per active AUV, run with summaries: the batch's episodes i*K .. i*K+K-1 are AUV act[i]'s, each from its

@@ -8,6 +8,8 @@ N particles per GPU.  Both stages stay on the device: the particle state the fil
 the planner batch reads its goals from (auvp_prrt_replan_particles); nothing but the per-step measurements goes in
 and nothing but the result records comes out.
 """
+import math
+
 import numpy as np
 
 from . import _pf_lib
@@ -91,3 +93,131 @@ class ParticleReplanner:
         summ = self.planner.plan()
         self.plan_ms = self.ctx.last_kernel_ms()
         return summ
+
+
+# ---- closed-loop fleet tracking: measure -> filter -> forecast -> plan, every round, on the device -------------------------------
+
+def shark_members(shark_of, n_sharks=None):
+    """members [F, A]: row f lists the AUVs with shark_of == f in ascending AUV index.  Every shark 0 .. F-1 must be tracked by
+    the same number A >= 1 of AUVs (F = n_sharks, or the largest label + 1); ValueError otherwise, for a label that is no
+    integer or lies outside [0, F).  csrc/replan_measure.h: replan_measure_members."""
+    so = list(shark_of)
+    for i, g in enumerate(so):
+        if isinstance(g, (bool, np.bool_)) or int(g) != g:
+            raise ValueError("shark_of[%d] = %r is not an integer" % (i, g))
+    so = [int(g) for g in so]
+    if not so:
+        raise ValueError("shark_of is empty")
+    F = max(so) + 1 if n_sharks is None else int(n_sharks)
+    if F < 1 or min(so) < 0 or max(so) >= F:
+        raise ValueError("shark_of must lie in [0, %d)" % F)
+    rows = [[] for _ in range(F)]
+    for i, g in enumerate(so):  # (ascending AUV index within every shark)
+        rows[g].append(i)
+    A = len(rows[0])
+    if A < 1 or any(len(r) != A for r in rows):
+        raise ValueError("every shark must be tracked by the same number of AUVs, not %r" % ([len(r) for r in rows],))
+    return np.array(rows, dtype=np.int32).reshape(F, A)
+
+
+def fleet_measurements(last7, shark_of, shark_xy):
+    """The range / bearing measurements of a fleet from its committed states -- the definition replan_measure_kernel is held
+    to.  last7 [N,7] (x, y, theta, ...), shark_of [N], shark_xy [F,2] the sharks' true positions.  Returns meas [1, F, A, 5]
+    (one step of `FilterBatch.run`): row (f, a) is the a-th AUV, in ascending index, of those tracking shark f --
+    x, y, theta, range = math.sqrt(dx*dx + dy*dy), bearing = math.atan2(dy, dx) - theta with dx = shark_x - x, dy = shark_y - y.
+    ValueError unless every shark is tracked by the same number of AUVs (shark_members)."""
+    last = np.asarray(last7, dtype=np.float64).reshape(-1, 7)
+    xy = np.asarray(shark_xy, dtype=np.float64).reshape(-1, 2)
+    if len(list(shark_of)) != len(last):
+        raise ValueError("shark_of has %d entries, last7 %d rows" % (len(list(shark_of)), len(last)))
+    mem = shark_members(shark_of, len(xy))
+    F, A = mem.shape
+    meas = np.zeros((1, F, A, 5))
+    for f in range(F):
+        sx, sy = float(xy[f, 0]), float(xy[f, 1])
+        for a in range(A):
+            x, y, theta = (float(v) for v in last[mem[f, a], :3])
+            dx, dy = sx - x, sy - y
+            meas[0, f, a] = (x, y, theta, math.sqrt(dx * dx + dy * dy), math.atan2(dy, dx) - theta)
+    return meas
+
+
+def first_bin_of_time(bins, t):
+    """index of the first bin [t0, t1] of bins [T,2] with t0 <= t <= t1; T - 1 where there is none (past the end)"""
+    b = np.asarray(bins, dtype=np.float64).reshape(-1, 2)
+    hit = np.flatnonzero((b[:, 0] <= t) & (t <= b[:, 1]))
+    return int(hit[0]) if len(hit) else len(b) - 1
+
+
+class FleetTracker:
+    """A fleet that tracks F sharks in a closed loop on the device.  Three contexts hold the state; what the loop itself moves
+    across the bus in a round is the sharks' true positions (F x 2 doubles in) and the round records (128 bytes per AUV out).
+    (`SharkForecast.run` still returns `prob` on the host as well -- the fallback of the hand-over and the final costs read it;
+    DESIGN.md.)
+
+        planner context (rrt)       the fleet's committed states, habitat lists and trajectory log (ReplanSession), the F shark
+                                    tables the planner ranks against, the measurement table of the round
+        filter context (filters)    the particles and their random streams (FilterBatch); the forecast's tables (SharkForecast
+                                    on the same context)
+        cost context (rrt's own)    the trajectories' final costs, at finish
+
+    step() with r = session.round_index:
+      1. meas [1, F, A, 5] from the AUVs' committed states against tracks[:, r] -- measure="device": replan_measure_kernel on
+         the planner's context, handed to the filters' context as a device pointer (auvp_pf_run_dev_meas); measure="host":
+         fleet_measurements on the host's mirror of the states and FilterBatch.run(meas=...) (the baseline, for tests);
+      2. forecast.run(filters, prior, forecast_rounds, method, return_grids=False);
+      3. session.set_shark_grids(fc, first_bin=b_r), b_r the first world bin that contains r * round_span (the last bin past
+         the end): the forecast speaks from now on;
+      4. session.round().
+    Limits: every shark is tracked by the same number of AUVs (ValueError); one filter step per round; b_r comes from the
+    NOMINAL time r * round_span, not from the AUVs' own clocks (their committed times drift apart by less than a round).
+    tracks [F, S, 2]; shark_of [N]; the remaining keyword arguments are RRT.replanning_session's (shark_of is passed on)."""
+
+    def __init__(self, rrt, forecast, filters, tracks, shark_of, prior, forecast_rounds, method=("ave", 1), measure="device",
+                 large_grids=False, **session_args):
+        if measure not in ("device", "host"):
+            raise ValueError("measure must be 'device' or 'host', not %r" % (measure,))
+        self.tracks = np.asarray(tracks, dtype=np.float64)
+        if self.tracks.ndim != 3 or self.tracks.shape[2] != 2:
+            raise ValueError("tracks must be [F, S, 2]")
+        F = self.tracks.shape[0]
+        if F != filters.F:
+            raise ValueError("tracks has %d sharks, the filter batch %d" % (F, filters.F))
+        self.members = shark_members(shark_of, F)  # (before anything is launched)
+        self.shark_of = np.array([int(g) for g in shark_of], dtype=np.int32)
+        self.A = self.members.shape[1]
+        self.rrt, self.forecast, self.filters = rrt, forecast, filters
+        self.prior, self.forecast_rounds, self.method, self.measure, self.large_grids = prior, int(forecast_rounds), method, measure, large_grids
+        # the planner needs F tables before a session with shark_of can open: the forecast of the filters as they stand
+        rrt.set_shark_grids(self._forecast(), first_bin=0)
+        self.session = rrt.replanning_session(shark_of=[int(g) for g in shark_of], **session_args)
+
+    def _forecast(self):
+        return self.forecast.run(self.filters, self.prior, self.forecast_rounds, self.method, large_grids=self.large_grids,
+                                 return_grids=False)
+
+    def step(self):
+        """one round of the loop; the round's dict (ReplanSession.round) plus estimates [F,2], the filters' means after the
+        update -- or None once no AUV plans any more or the tracks have ended"""
+        s = self.session
+        r = s.round_index
+        if r >= self.tracks.shape[1] or len(s.active()) == 0:
+            return None
+        shark = self.tracks[:, r, :]
+        if self.measure == "device":
+            ptr = self.rrt._ctx.replan_measure(self.shark_of, self.A, shark)
+            self.filters.run_dev_meas(ptr, self.A, shark[None])
+        else:
+            self.filters.run(meas=fleet_measurements(s.last, self.shark_of, shark), shark_xy=shark[None])
+        fc = self._forecast()
+        s.set_shark_grids(fc, first_bin=first_bin_of_time(self.rrt._bins, r * s.round_span))
+        out = s.round()
+        if out is not None:
+            out["estimates"] = self.filters.estimates()[0][0]
+        return out
+
+    def run(self, as_arrays=False):
+        """step() until the session is done or the tracks end; returns session.finish(as_arrays)"""
+        while self.step() is not None:
+            pass
+        return self.session.finish(as_arrays)

@@ -190,6 +190,18 @@ int auvp_rrt_group_paths_dev(auvp_handle* h, const int64_t* offsets, void* out_d
  * leaf pass's error bound, each episode's own.  A later auvp_world_set drops the sets; auvp_world_set_habitats keeps them.
  * The tree growth never reads a probability table: only the leaf ranking depends on the set. */
 int auvp_world_set_prob_sets(auvp_handle* h, int32_t n_sets, const double* prob_host, const void* prob_dev);
+/* The sets from a forecast whose rounds are counted from "now", placed at the world's absolute bins (csrc/forecast_place.h):
+ * prob_dev is a device pointer to [n_sets, n_rounds1, n_cells] on the handle's device (auvp_sf_prob_dev of the forecast's handle);
+ * with T world bins, bin t of every set becomes forecast round min(max(t - first_bin, 0), n_rounds1 - 1).  sf_place_kernel gathers
+ * on the device, one workgroup per (set, bin) row with 16-byte loads and stores, into the buffer the handle owns; the per-set
+ * constants are computed as in auvp_world_set_prob_sets.  first_bin == 0 with n_rounds1 == T is auvp_world_set_prob_sets(h, n_sets,
+ * NULL, prob_dev) itself.  AUVP_ERR_ARG: a null pointer, n_sets or n_rounds1 < 1, n_cells not the world's, first_bin outside
+ * 0 .. T - 1; AUVP_ERR_STATE without a world that has bins and cells.  A call that fails launches nothing and keeps the sets. */
+int auvp_world_set_prob_sets_placed(auvp_handle* h, const void* prob_dev, int32_t n_sets, int32_t n_rounds1, int32_t n_cells,
+                                    int32_t first_bin);
+/* The sets as they lie in HBM, copied to the host (for checks): n_sets, prob [n_sets, T, C]; each may be NULL.  AUVP_ERR_STATE
+ * without sets. */
+int auvp_world_prob_sets_read(auvp_handle* h, int32_t* n_sets, double* prob);
 /* the per-set constants, absmax [n_sets] and one_sign [n_sets] (each may be NULL); AUVP_ERR_STATE without sets */
 int auvp_world_prob_set_stats(auvp_handle* h, double* absmax, int32_t* one_sign);
 /* After auvp_rrt_prepare_episodes and before auvp_rrt_run: episode e ranks its leaves against set set_of[e].  An index outside
@@ -252,6 +264,21 @@ int auvp_replan_team_fold(auvp_handle* h, int32_t n, const int32_t* team_of, uin
  * [0, n_auvs), an AUV named twice, round_span not > 0.  A call that fails launches nothing and changes no state. */
 int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of /* [n_active] */, double round_span,
                        auvp_replan_record* out /* [n_active], may be NULL */);
+/* The fleet's range / bearing measurements of the sharks it tracks, from the states it has committed (csrc/replan_measure.h;
+ * replan_measure_kernel, one lane per row).  shark_of [n_auvs]: the shark AUV a tracks; every shark 0 .. n_auvs / n_per_shark - 1
+ * must be tracked by exactly n_per_shark AUVs, taken in ascending AUV index (anything else: AUVP_ERR_ARG).  shark_xy [F,2]: the
+ * sharks' true positions (the only input that crosses the bus).  Row (f, a) of the table [F, n_per_shark, 5] the handle keeps in
+ * HBM: the AUV's x, y, theta, range = sqrt(dx*dx + dy*dy), bearing = atan2(dy, dx) - theta, dx = shark_x - x (the layout of
+ * auvp_pf_run's meas for one step; the square root correctly rounded, the atan2 the particle-filter kernel's value rounded
+ * to the nearest double -- csrc/replan_measure.h: what math.sqrt and math.atan2 give).  An AUV that no longer plans keeps measuring
+ * from its last committed state.  *meas_dev_out (may be NULL) gets the table's device pointer: valid until the next
+ * auvp_replan_measure or auvp_replan_begin on this handle; the call synchronises its stream before it returns, so a copy enqueued
+ * afterwards on another handle's stream on the same device is ordered behind it.  AUVP_ERR_STATE without auvp_replan_begin. */
+int auvp_replan_measure(auvp_handle* h, const int32_t* shark_of /* [n_auvs] */, int32_t n_per_shark, const double* shark_xy /* [F,2] */,
+                        const void** meas_dev_out);
+/* The last auvp_replan_measure's table copied to the host (for checks): n_sharks, n_per_shark, meas [F, n_per_shark, 5]; each may
+ * be NULL.  AUVP_ERR_STATE without one since auvp_replan_begin. */
+int auvp_replan_meas(auvp_handle* h, int32_t* n_sharks, int32_t* n_per_shark, double* meas);
 /* The team-aware winner selection ("claims", csrc/replan_pick.h), in place of auvp_rrt_group_best in a round: the batch that
  * just ran holds K trees for each of n_active AUVs, group g = episodes g*K .. g*K+K-1 = AUV auv_of[g].  Every group first gets
  * rrt_group_best_kernel's record.  Then, for every team of two or more (auvp_replan_set_teams), the members that are part of
@@ -538,6 +565,11 @@ int auvp_pf_set_rng(auvp_handle* h, const uint32_t* mt_key, const int32_t* mt_po
  * list_of_new_particles (numpy raises ValueError). */
 int auvp_pf_run(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const double* meas,
                 const double* shark_xy, int32_t flags);
+/* auvp_pf_run with meas [S,F,n_auv,5] already in HBM on this handle's device (auvp_replan_measure of a planner's handle): copied
+ * device to device into the handle's own buffer on its stream, so the producer's buffer is free again when the call returns.  The
+ * producer must have synchronised its stream (auvp_replan_measure does).  Everything else as auvp_pf_run. */
+int auvp_pf_run_dev_meas(auvp_handle* h, int32_t n_steps, int32_t n_auv, int32_t phases, const void* meas_dev,
+                         const double* shark_xy, int32_t flags);
 int auvp_pf_particles(auvp_handle* h, double* particles, int32_t* obj);
 /* device-resident state for a caller that keeps working on the GPU: SoA [F][5][N] doubles, ids [F][N] */
 int auvp_pf_particles_dev(auvp_handle* h, double** particles_soa, int32_t** obj);
