@@ -92,6 +92,34 @@ int replan_log_reserve(auvp_handle* h, ReplanState& S, long long rows) {
   return AUVP_OK;
 }
 
+// slot_of [n_auvs]: the group that names each AUV, -1: none; every auv_of[g] inside [0, n_auvs) and named once
+int replan_slot_of(auvp_handle* h, const int32_t* auv_of, int G, int n_auvs, std::vector<int32_t>& slot_of) {
+  slot_of.assign((size_t)n_auvs, -1);
+  for (int g = 0; g < G; g++) {
+    const int a = auv_of[g];
+    if (a < 0 || a >= n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, n_auvs);
+    if (slot_of[(size_t)a] >= 0) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
+    slot_of[(size_t)a] = (int32_t)g;
+  }
+  return AUVP_OK;
+}
+
+// course_off [n + 1]: row offsets from 0, ascending, no course of 2^31 rows or more
+int replan_course_off_check(auvp_handle* h, const int64_t* course_off, int n) {
+  if (course_off[0] != 0) return fail(h, AUVP_ERR_ARG, "course_off[0] != 0");
+  for (int i = 0; i < n; i++)
+    if (course_off[i + 1] < course_off[i] || course_off[i + 1] - course_off[i] > 0x7fffffffll)
+      return fail(h, AUVP_ERR_ARG, "course_off is not an ascending list of row offsets");
+  return AUVP_OK;
+}
+
+// members of the largest team
+int replan_max_team(const auvp::ReplanTeamCsr& csr) {
+  int n = 0;
+  for (int t = 0; t < csr.n_teams(); t++) n = std::max(n, (int)(csr.team_off[(size_t)t + 1] - csr.team_off[(size_t)t]));
+  return n;
+}
+
 // rrt_commit_kernel on the slots and, with `teams`, replan_team_kernel on the fleet's teams behind it, timed together; the
 // records come back into S.rec_host
 int replan_launch(auvp_handle* h, ReplanState& S, const auvp::RrtBuffers* B, auvp::ReplanCommitDev& A, const std::vector<auvp::ReplanSlot>& slots,
@@ -239,8 +267,7 @@ int auvp_replan_set_teams(auvp_handle* h, int32_t n_auvs, const int32_t* team_of
   std::swap(S.team_off.p, off.p); std::swap(S.team_off.cap, off.cap);
   std::swap(S.team_members.p, mem.p); std::swap(S.team_members.cap, mem.cap);
   S.n_teams = csr.n_teams();
-  S.max_team = 0;
-  for (int t = 0; t < csr.n_teams(); t++) S.max_team = std::max(S.max_team, (int)(csr.team_off[(size_t)t + 1] - csr.team_off[(size_t)t]));
+  S.max_team = replan_max_team(csr);
   return AUVP_OK;
 }
 
@@ -283,13 +310,9 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
   if (n_active != G) return fail(h, AUVP_ERR_ARG, "n_active %d, the batch has %d groups", n_active, G);
   if (!auv_of) return fail(h, AUVP_ERR_ARG, "auv_of is null");
   if (!(round_span > 0.0)) return fail(h, AUVP_ERR_ARG, "round_span must be > 0");
-  std::vector<char> seen((size_t)S.n_auvs, 0);
-  for (int g = 0; g < G; g++) {
-    const int a = auv_of[g];
-    if (a < 0 || a >= S.n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, S.n_auvs);
-    if (seen[(size_t)a]) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
-    seen[(size_t)a] = 1;
-  }
+  int rc;
+  std::vector<int32_t> slot_of;
+  if ((rc = replan_slot_of(h, auv_of, G, S.n_auvs, slot_of))) return rc;
   // the slots, from the host's copy of the group records: a group that failed or has no winner commits nothing
   std::vector<auvp::ReplanSlot> slots((size_t)G);
   long long total = 0;
@@ -302,7 +325,6 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
     total += s.path_len;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  int rc;
   if ((rc = replan_log_reserve(h, S, S.log_rows + total))) return rc;
   HIPCHK(h, S.course.reserve((size_t)std::max<long long>(total, 1) * auvp::REPLAN_ROW * sizeof(double)));
   auvp::ReplanCommitDev A{};
@@ -346,6 +368,44 @@ int replan_apart_check(auvp_handle* h, const ReplanApartArgs* ap, int max_team) 
   return AUVP_OK;
 }
 
+// what the tick tables' kernel and the pick that reads them share: the window and the tables' place
+void replan_apart_fill(const ReplanApartArgs& ap, int E, int K, int32_t* head, double* xy, int32_t* conflicts, auvp::ReplanTicksDev& C,
+                       auvp::ReplanApartDev& D) {
+  C.n_episodes = E; C.K = K; C.W = ap.W; C.tick = ap.tick;
+  C.head = head; C.xy = xy;
+  D.W = ap.W; D.use_claims = ap.use_claims ? 1 : 0; D.d2 = ap.d * ap.d;
+  D.head = head; D.xy = xy; D.conflicts = conflicts;
+}
+
+// The pick's launches on h->stream: rrt_group_best_kernel's record for every group of T.K of T's summaries -- the pick rewrites
+// those of the members of teams of two or more --, then, between ev0 and ev1, the words (A; null: nobody reads them) and, with D,
+// the tick tables C and the pick that keeps courses apart, without it the pick by the claims.  B: the batch's trees; null: the
+// probe's courses.
+int replan_pick_enqueue(auvp_handle* h, const auvp::RrtBuffers* B, const int32_t* group_off, const auvp::ReplanWordsDev* A,
+                        const auvp::ReplanTicksDev* C, const auvp::ReplanApartDev* D, const auvp::ReplanPickDev& T) {
+  const int G = T.n_slots;
+  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
+                     T.summary, group_off, T.best, G);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  if (A) HIPCHK(h, auvpi_replan_words_launch(B, A, h->stream));
+  if (D) {
+    HIPCHK(h, auvpi_replan_ticks_launch(B, C, h->stream));
+    HIPCHK(h, auvpi_replan_pick_apart_launch(&T, D, h->stream));
+  } else {
+    HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
+  }
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return AUVP_OK;
+}
+
+// [G + 1] offsets of groups of K episodes each
+std::vector<int32_t> replan_group_off(int G, int K) {
+  std::vector<int32_t> off((size_t)G + 1);
+  for (int g = 0; g <= G; g++) off[(size_t)g] = (int32_t)(g * K);
+  return off;
+}
+
 // auvp_replan_team_pick (ap == null) and auvp_replan_team_pick_apart
 int replan_team_pick_impl(auvp_handle* h, int32_t n_active, const int32_t* auv_of, int32_t K, const ReplanApartArgs* ap,
                           struct auvp_rrt_group_best* out) {
@@ -362,15 +422,9 @@ int replan_team_pick_impl(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   int rc;
   if ((rc = replan_apart_check(h, ap, S.max_team))) return rc;
   const bool words = !ap || ap->use_claims;  // (without the claims nobody reads the words: no launch, no scratch for them)
-  std::vector<int32_t> slot_of((size_t)S.n_auvs, -1);
-  for (int g = 0; g < G; g++) {
-    const int a = auv_of[g];
-    if (a < 0 || a >= S.n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, S.n_auvs);
-    if (slot_of[(size_t)a] >= 0) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
-    slot_of[(size_t)a] = (int32_t)g;
-  }
-  std::vector<int32_t> group_off((size_t)G + 1);
-  for (int g = 0; g <= G; g++) group_off[(size_t)g] = (int32_t)(g * K);
+  std::vector<int32_t> slot_of;
+  if ((rc = replan_slot_of(h, auv_of, G, S.n_auvs, slot_of))) return rc;
+  const std::vector<int32_t> group_off = replan_group_off(G, K);
   HIPCHK(h, hipSetDevice(h->device));
   // a course has at most one element per node and per path point of its tree: the scratch is sized from the batch's capacities
   // (the summaries stay in HBM), the same place for every episode
@@ -408,25 +462,10 @@ int replan_team_pick_impl(auvp_handle* h, int32_t n_active, const int32_t* auv_o
   auvp::ReplanTicksDev C{};
   auvp::ReplanApartDev D{};
   if (ap) {
-    C.n_episodes = E; C.K = K; C.W = ap->W; C.tick = ap->tick;
+    replan_apart_fill(*ap, E, K, S.tick_head.as<int32_t>(), S.tick_xy.as<double>(), S.conflicts.as<int32_t>(), C, D);
     C.auv_of = A.auv_of; C.last = A.last;
-    C.head = S.tick_head.as<int32_t>(); C.xy = S.tick_xy.as<double>();
-    D.W = ap->W; D.use_claims = ap->use_claims ? 1 : 0; D.d2 = ap->d * ap->d;
-    D.head = C.head; D.xy = C.xy; D.conflicts = S.conflicts.as<int32_t>();
   }
-  // every group gets rrt_group_best_kernel's record; the pick rewrites those of the members of teams of two or more
-  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
-                     h->B.summary, h->d_group_off.as<int32_t>(), h->d_group_best.as<RrtGroupBest>(), G);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  if (words) HIPCHK(h, auvpi_replan_words_launch(&h->B, &A, h->stream));
-  if (ap) {
-    HIPCHK(h, auvpi_replan_ticks_launch(&h->B, &C, h->stream));
-    HIPCHK(h, auvpi_replan_pick_apart_launch(&T, &D, h->stream));
-  } else {
-    HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
-  }
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  if ((rc = replan_pick_enqueue(h, &h->B, h->d_group_off.as<int32_t>(), words ? &A : nullptr, &C, ap ? &D : nullptr, T))) return rc;
   h->group_best.resize((size_t)G);
   HIPCHK(h, hipMemcpyAsync(h->group_best.data(), h->d_group_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -447,7 +486,93 @@ int replan_team_pick_courses_impl(auvp_handle* h, int32_t n_auvs, const int32_t*
                                   const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
                                   const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
                                   const int32_t* bin_hi, const double* weights3, const ReplanApartArgs* ap,
-                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out);
+                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out) {
+  if (!h) return AUVP_ERR_ARG;
+  if (n_auvs < 1 || n_active < 1 || K < 1 || !team_of || !keep || !auv_of || !course_off || !cost4 || !leaf_t || !bin_lo || !bin_hi ||
+      !weights3 || !out || !claimed_out)
+    return fail(h, AUVP_ERR_ARG, "bad probe arguments");
+  if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
+  if ((long long)n_active * K > 0x7fffffffll) return fail(h, AUVP_ERR_ARG, "too many candidates");
+  const int G = n_active, E = n_active * K;
+  int rc;
+  std::vector<int32_t> slot_of;
+  if ((rc = replan_slot_of(h, auv_of, G, n_auvs, slot_of))) return rc;
+  if ((rc = replan_course_off_check(h, course_off, E))) return rc;
+  const long long total = course_off[E];
+  if (total > 0 && !courses_xyt) return fail(h, AUVP_ERR_ARG, "courses_xyt is null");
+  for (int e = 0; e < E; e++)
+    if (bin_lo[e] < 0 || bin_hi[e] > h->W.n_bins) return fail(h, AUVP_ERR_ARG, "candidate %d: bins %d .. %d outside the table of %d", e, bin_lo[e], bin_hi[e], h->W.n_bins);
+  // the candidates as summaries: what the two selection kernels read of one
+  std::vector<RrtSummary> summ((size_t)E);
+  std::vector<int32_t> len((size_t)E);
+  const std::vector<int32_t> group_off = replan_group_off(G, K);
+  memset(summ.data(), 0, summ.size() * sizeof(RrtSummary));
+  for (int e = 0; e < E; e++) {
+    const int L = (int)(course_off[e + 1] - course_off[e]);
+    len[(size_t)e] = L;
+    RrtSummary& s = summ[(size_t)e];
+    s.best_leaf = L > 0 ? 0 : -1;
+    s.best_path_len = L;
+    for (int k = 0; k < 4; k++) s.best_cost[k] = cost4[4 * (size_t)e + k];
+    s.best_length = length ? length[e] : 0.0;
+  }
+  const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
+  if ((rc = replan_apart_check(h, ap, replan_max_team(csr)))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  // the probe's own buffers: the fleet's state, the handle's group records and the counters stay as they are
+  DevBuf d_summ, d_len, d_goff, d_off, d_xyt, d_lt, d_lo, d_hi, d_keep, d_slot, d_toff, d_tmem, d_words, d_best, d_claimed, d_thead, d_txy, d_conf;
+  if ((rc = upload(h, d_summ, summ.data(), summ.size()))) return rc;
+  if ((rc = upload(h, d_len, len.data(), len.size()))) return rc;
+  if ((rc = upload(h, d_goff, group_off.data(), group_off.size()))) return rc;
+  if ((rc = upload(h, d_off, course_off, (size_t)E + 1))) return rc;
+  if ((rc = upload(h, d_xyt, courses_xyt, (size_t)total * 3))) return rc;
+  if ((rc = upload(h, d_lt, leaf_t, (size_t)E))) return rc;
+  if ((rc = upload(h, d_lo, bin_lo, (size_t)E))) return rc;
+  if ((rc = upload(h, d_hi, bin_hi, (size_t)E))) return rc;
+  if ((rc = upload(h, d_keep, keep, (size_t)n_auvs))) return rc;
+  if ((rc = upload(h, d_slot, slot_of.data(), slot_of.size()))) return rc;
+  if ((rc = upload(h, d_toff, csr.team_off.data(), csr.team_off.size()))) return rc;
+  if ((rc = upload(h, d_tmem, csr.members.data(), csr.members.size()))) return rc;
+  HIPCHK(h, d_words.reserve((size_t)std::max<long long>(total, 1) * sizeof(uint64_t)));
+  HIPCHK(h, d_best.reserve((size_t)G * sizeof(RrtGroupBest)));
+  HIPCHK(h, d_claimed.reserve((size_t)G * sizeof(uint64_t)));
+  HIPCHK(h, hipMemsetAsync(d_claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
+  auvp::ReplanTicksDev C{};
+  auvp::ReplanApartDev D{};
+  if (ap) {
+    HIPCHK(h, d_thead.reserve((size_t)E * 2 * sizeof(int32_t)));
+    HIPCHK(h, d_txy.reserve((size_t)E * (size_t)ap->W * 2 * sizeof(double)));
+    HIPCHK(h, d_conf.reserve((size_t)G * sizeof(int32_t)));
+    HIPCHK(h, hipMemsetAsync(d_conf.p, 0, (size_t)G * sizeof(int32_t), h->stream));
+    replan_apart_fill(*ap, E, K, d_thead.as<int32_t>(), d_txy.as<double>(), d_conf.as<int32_t>(), C, D);
+    C.from_courses = 1;
+    C.off = d_off.as<int64_t>(); C.xyt = d_xyt.as<double>(); C.len = d_len.as<int32_t>();
+  }
+  auvp::ReplanWordsDev A{};
+  A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
+  A.from_courses = 1;
+  A.off = d_off.as<int64_t>(); A.xyt = d_xyt.as<double>(); A.len = d_len.as<int32_t>();
+  A.bin_lo = d_lo.as<int32_t>(); A.bin_hi = d_hi.as<int32_t>();
+  A.hab = h->W.hab; A.hab_t = h->W.hab_t; A.bins = h->W.bins;
+  A.words = d_words.as<uint64_t>();
+  auvp::ReplanPickDev T{};
+  T.n_teams = csr.n_teams(); T.K = K; T.n_slots = G;
+  T.team_off = d_toff.as<int32_t>(); T.members = d_tmem.as<int32_t>(); T.slot_of = d_slot.as<int32_t>();
+  T.keep = d_keep.as<uint64_t>();
+  T.summary = d_summ.as<RrtSummary>();
+  T.words = A.words; T.off = A.off; T.leaf_t = d_lt.as<double>();
+  T.best = d_best.as<RrtGroupBest>(); T.claimed = d_claimed.as<uint64_t>();
+  T.w1 = weights3[0]; T.w2 = weights3[1];
+  if ((rc = replan_pick_enqueue(h, nullptr, d_goff.as<int32_t>(), &A, &C, ap ? &D : nullptr, T))) return rc;
+  HIPCHK(h, hipMemcpyAsync(out, d_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(claimed_out, d_claimed.p, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  if (ap) HIPCHK(h, hipMemcpyAsync(conflicts_out, d_conf.p, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
+  return AUVP_OK;
+}
 
 }  // namespace
 
@@ -482,128 +607,6 @@ int auvp_replan_team_pick_apart_courses(auvp_handle* h, int32_t n_auvs, const in
   return replan_team_pick_courses_impl(h, n_auvs, team_of, keep, n_active, auv_of, K, course_off, courses_xyt, cost4, leaf_t, length, bin_lo,
                                        bin_hi, weights3, &ap, out, claimed_out, conflicts_out);
 }
-
-}  // extern "C"
-
-namespace {
-
-int replan_team_pick_courses_impl(auvp_handle* h, int32_t n_auvs, const int32_t* team_of, const uint64_t* keep, int32_t n_active,
-                                  const int32_t* auv_of, int32_t K, const int64_t* course_off, const double* courses_xyt,
-                                  const double* cost4, const double* leaf_t, const double* length, const int32_t* bin_lo,
-                                  const int32_t* bin_hi, const double* weights3, const ReplanApartArgs* ap,
-                                  struct auvp_rrt_group_best* out, uint64_t* claimed_out, int32_t* conflicts_out) {
-  if (!h) return AUVP_ERR_ARG;
-  if (n_auvs < 1 || n_active < 1 || K < 1 || !team_of || !keep || !auv_of || !course_off || !cost4 || !leaf_t || !bin_lo || !bin_hi ||
-      !weights3 || !out || !claimed_out)
-    return fail(h, AUVP_ERR_ARG, "bad probe arguments");
-  if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
-  if ((long long)n_active * K > 0x7fffffffll) return fail(h, AUVP_ERR_ARG, "too many candidates");
-  const int G = n_active, E = n_active * K;
-  std::vector<int32_t> slot_of((size_t)n_auvs, -1);
-  for (int g = 0; g < G; g++) {
-    const int a = auv_of[g];
-    if (a < 0 || a >= n_auvs) return fail(h, AUVP_ERR_ARG, "group %d: AUV %d outside [0, %d)", g, a, n_auvs);
-    if (slot_of[(size_t)a] >= 0) return fail(h, AUVP_ERR_ARG, "AUV %d is named twice", a);
-    slot_of[(size_t)a] = (int32_t)g;
-  }
-  if (course_off[0] != 0) return fail(h, AUVP_ERR_ARG, "course_off[0] != 0");
-  for (int e = 0; e < E; e++)
-    if (course_off[e + 1] < course_off[e] || course_off[e + 1] - course_off[e] > 0x7fffffffll)
-      return fail(h, AUVP_ERR_ARG, "course_off is not an ascending list of row offsets");
-  const long long total = course_off[E];
-  if (total > 0 && !courses_xyt) return fail(h, AUVP_ERR_ARG, "courses_xyt is null");
-  for (int e = 0; e < E; e++)
-    if (bin_lo[e] < 0 || bin_hi[e] > h->W.n_bins) return fail(h, AUVP_ERR_ARG, "candidate %d: bins %d .. %d outside the table of %d", e, bin_lo[e], bin_hi[e], h->W.n_bins);
-  // the candidates as summaries: what the two selection kernels read of one
-  std::vector<RrtSummary> summ((size_t)E);
-  std::vector<int32_t> len((size_t)E), group_off((size_t)G + 1);
-  memset(summ.data(), 0, summ.size() * sizeof(RrtSummary));
-  for (int e = 0; e < E; e++) {
-    const int L = (int)(course_off[e + 1] - course_off[e]);
-    len[(size_t)e] = L;
-    RrtSummary& s = summ[(size_t)e];
-    s.best_leaf = L > 0 ? 0 : -1;
-    s.best_path_len = L;
-    for (int k = 0; k < 4; k++) s.best_cost[k] = cost4[4 * (size_t)e + k];
-    s.best_length = length ? length[e] : 0.0;
-  }
-  for (int g = 0; g <= G; g++) group_off[(size_t)g] = (int32_t)(g * K);
-  const auvp::ReplanTeamCsr csr = auvp::replan_team_csr(team_of, n_auvs);
-  int rc, max_team = 0;
-  for (int t = 0; t < csr.n_teams(); t++) max_team = std::max(max_team, (int)(csr.team_off[(size_t)t + 1] - csr.team_off[(size_t)t]));
-  if ((rc = replan_apart_check(h, ap, max_team))) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  // the probe's own buffers: the fleet's state, the handle's group records and the counters stay as they are
-  DevBuf d_summ, d_len, d_goff, d_off, d_xyt, d_lt, d_lo, d_hi, d_keep, d_slot, d_toff, d_tmem, d_words, d_best, d_claimed, d_thead, d_txy, d_conf;
-  if ((rc = upload(h, d_summ, summ.data(), summ.size()))) return rc;
-  if ((rc = upload(h, d_len, len.data(), len.size()))) return rc;
-  if ((rc = upload(h, d_goff, group_off.data(), group_off.size()))) return rc;
-  if ((rc = upload(h, d_off, course_off, (size_t)E + 1))) return rc;
-  if ((rc = upload(h, d_xyt, courses_xyt, (size_t)total * 3))) return rc;
-  if ((rc = upload(h, d_lt, leaf_t, (size_t)E))) return rc;
-  if ((rc = upload(h, d_lo, bin_lo, (size_t)E))) return rc;
-  if ((rc = upload(h, d_hi, bin_hi, (size_t)E))) return rc;
-  if ((rc = upload(h, d_keep, keep, (size_t)n_auvs))) return rc;
-  if ((rc = upload(h, d_slot, slot_of.data(), slot_of.size()))) return rc;
-  if ((rc = upload(h, d_toff, csr.team_off.data(), csr.team_off.size()))) return rc;
-  if ((rc = upload(h, d_tmem, csr.members.data(), csr.members.size()))) return rc;
-  HIPCHK(h, d_words.reserve((size_t)std::max<long long>(total, 1) * sizeof(uint64_t)));
-  HIPCHK(h, d_best.reserve((size_t)G * sizeof(RrtGroupBest)));
-  HIPCHK(h, d_claimed.reserve((size_t)G * sizeof(uint64_t)));
-  HIPCHK(h, hipMemsetAsync(d_claimed.p, 0, (size_t)G * sizeof(uint64_t), h->stream));
-  auvp::ReplanTicksDev C{};
-  auvp::ReplanApartDev D{};
-  if (ap) {
-    HIPCHK(h, d_thead.reserve((size_t)E * 2 * sizeof(int32_t)));
-    HIPCHK(h, d_txy.reserve((size_t)E * (size_t)ap->W * 2 * sizeof(double)));
-    HIPCHK(h, d_conf.reserve((size_t)G * sizeof(int32_t)));
-    HIPCHK(h, hipMemsetAsync(d_conf.p, 0, (size_t)G * sizeof(int32_t), h->stream));
-    C.n_episodes = E; C.K = K; C.W = ap->W; C.from_courses = 1; C.tick = ap->tick;
-    C.off = d_off.as<int64_t>(); C.xyt = d_xyt.as<double>(); C.len = d_len.as<int32_t>();
-    C.head = d_thead.as<int32_t>(); C.xy = d_txy.as<double>();
-    D.W = ap->W; D.use_claims = ap->use_claims ? 1 : 0; D.d2 = ap->d * ap->d;
-    D.head = C.head; D.xy = C.xy; D.conflicts = d_conf.as<int32_t>();
-  }
-  auvp::ReplanWordsDev A{};
-  A.n_episodes = E; A.K = K; A.H = h->W.n_habitats; A.n_bins = h->W.n_bins;
-  A.from_courses = 1;
-  A.off = d_off.as<int64_t>(); A.xyt = d_xyt.as<double>(); A.len = d_len.as<int32_t>();
-  A.bin_lo = d_lo.as<int32_t>(); A.bin_hi = d_hi.as<int32_t>();
-  A.hab = h->W.hab; A.hab_t = h->W.hab_t; A.bins = h->W.bins;
-  A.words = d_words.as<uint64_t>();
-  auvp::ReplanPickDev T{};
-  T.n_teams = csr.n_teams(); T.K = K; T.n_slots = G;
-  T.team_off = d_toff.as<int32_t>(); T.members = d_tmem.as<int32_t>(); T.slot_of = d_slot.as<int32_t>();
-  T.keep = d_keep.as<uint64_t>();
-  T.summary = d_summ.as<RrtSummary>();
-  T.words = A.words; T.off = A.off; T.leaf_t = d_lt.as<double>();
-  T.best = d_best.as<RrtGroupBest>(); T.claimed = d_claimed.as<uint64_t>();
-  T.w1 = weights3[0]; T.w2 = weights3[1];
-  hipLaunchKernelGGL(rrt_group_best_kernel, dim3((G + RRT_GROUP_WAVES - 1) / RRT_GROUP_WAVES), dim3(RRT_GROUP_WAVES * 64), 0, h->stream,
-                     d_summ.as<RrtSummary>(), d_goff.as<int32_t>(), d_best.as<RrtGroupBest>(), G);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  HIPCHK(h, auvpi_replan_words_launch(nullptr, &A, h->stream));
-  if (ap) {
-    HIPCHK(h, auvpi_replan_ticks_launch(nullptr, &C, h->stream));
-    HIPCHK(h, auvpi_replan_pick_apart_launch(&T, &D, h->stream));
-  } else {
-    HIPCHK(h, auvpi_replan_pick_launch(&T, h->stream));
-  }
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out, d_best.p, (size_t)G * sizeof(RrtGroupBest), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(claimed_out, d_claimed.p, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-  if (ap) HIPCHK(h, hipMemcpyAsync(conflicts_out, d_conf.p, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms; h->last_grid = E; h->last_block = 64; h->last_lds = (int)(auvp::REPLAN_MAX_HAB * 4 * sizeof(double));
-  return AUVP_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int auvp_replan_traj(auvp_handle* h, int64_t* row_off, double* rows) {
   if (!h) return AUVP_ERR_ARG;
@@ -641,17 +644,14 @@ int auvp_replan_commit_courses(auvp_handle* h, int32_t n_states, const int64_t* 
   if (n_states < 1 || !course_off || !last7 || !keep || !out) return fail(h, AUVP_ERR_ARG, "bad probe arguments");
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   if (!(round_span > 0.0)) return fail(h, AUVP_ERR_ARG, "round_span must be > 0");
-  if (course_off[0] != 0) return fail(h, AUVP_ERR_ARG, "course_off[0] != 0");
-  for (int i = 0; i < n_states; i++)
-    if (course_off[i + 1] < course_off[i] || course_off[i + 1] - course_off[i] > 0x7fffffffll)
-      return fail(h, AUVP_ERR_ARG, "course_off is not an ascending list of row offsets");
+  int rc;
+  if ((rc = replan_course_off_check(h, course_off, n_states))) return rc;
   const long long total = course_off[n_states];
   if (total > 0 && (!courses || !rows_out)) return fail(h, AUVP_ERR_ARG, "courses / rows_out is null");
   HIPCHK(h, hipSetDevice(h->device));
   ReplanState& S = *replan_of(h);
   // the probe's own state arrays and row buffer: the fleet's (auvp_replan_begin) stay as they are
   DevBuf d_last, d_keep, d_rows;
-  int rc;
   if ((rc = upload(h, d_last, last7, (size_t)n_states * auvp::REPLAN_ROW))) return rc;
   if ((rc = upload(h, d_keep, keep, (size_t)n_states))) return rc;
   if ((rc = upload(h, S.course, courses, (size_t)total * auvp::REPLAN_ROW))) return rc;
