@@ -44,102 +44,37 @@ AstarState* astar_of(auvp_handle* h) {
   return static_cast<AstarState*>(h->astar);
 }
 
-// Python round(v, 2): decimal rounding of the exact binary value (float.__round__ -> dtoa mode 3)
-double round2_py(double v) {
-  char buf[512];
-  snprintf(buf, sizeof buf, "%.2f", v);
-  return strtod(buf, nullptr);
+// the visited words' next epoch (epoch_tag_next, batch_plan.h), clearing them where the rule says so
+int astar_next_epoch(auvp_handle* h, AstarState& S, bool new_buffer) {
+  const auvp::EpochTag next = auvp::epoch_tag_next(S.epoch, new_buffer);
+  if (next.clear) {
+    HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
+    S.cellinfo_clean_cap = S.cellinfo.cap;
+  }
+  S.epoch = next.tag;
+  return AUVP_OK;
 }
 
 int astar_build_world(auvp_handle* h, AstarState& S) {
   const int O = (int)(h->w_obst.size() / 3), H = (int)(h->w_hab.size() / 3), V = (int)(h->w_poly.size() / 2);
   const int T = (int)(h->w_bins.size() / 2), C = (int)(h->w_cells.size() / 4);
   if (H > auvp::ASTAR_MAX_HAB) return fail(h, AUVP_ERR_ARG, "n_habitats %d > %d", H, auvp::ASTAR_MAX_HAB);
-  std::vector<double> ox(O), oy(O), ot(O), hab((size_t)H * 4), rc((size_t)C * 4), topn((size_t)T * (C + 1));
-  for (int i = 0; i < O; i++) {
-    ox[i] = h->w_obst[3 * i]; oy[i] = h->w_obst[3 * i + 1];
-    ot[i] = auvp::sq_threshold(h->w_obst[3 * i + 2]);  // plain `d <= obstacle.size` per obstacle (no shared dList here)
-  }
-  for (int i = 0; i < H; i++) {
-    hab[4 * i] = h->w_hab[3 * i]; hab[4 * i + 1] = h->w_hab[3 * i + 1]; hab[4 * i + 2] = h->w_hab[3 * i + 2];
-    hab[4 * i + 3] = auvp::sq_threshold(h->w_hab[3 * i + 2]);
-  }
-  for (size_t i = 0; i < rc.size(); i++) rc[i] = round2_py(h->w_cells[i]);
-  auvp::astar_topn_rows(h->w_prob.data(), (size_t)T, (size_t)C, topn.data());  // get_top_n_prob's table (astar_tables.h)
-  // Polygon(...).centroid: area-weighted (shoelace) centroid -- shapely is absent; DESIGN.md
-  double a2 = 0.0, sx = 0.0, sy = 0.0;
-  for (int i = 0; i < V; i++) {
-    double x0 = h->w_poly[2 * i], y0 = h->w_poly[2 * i + 1];
-    double x1 = h->w_poly[2 * ((i + 1) % V)], y1 = h->w_poly[2 * ((i + 1) % V) + 1];
-    double cr = x0 * y1 - x1 * y0;
-    a2 += cr;
-    sx += (x0 + x1) * cr;
-    sy += (y0 + y1) * cr;
-  }
-  // product grid?  row-major list of ncol x nrow cells whose x interval depends on the column only and whose y interval
-  // on the row only, edges ascending, neighbouring intervals touching at most, no degenerate widths (astar_kernel.h)
-  int g_ncol = 0, g_nrow = 0;
-  std::vector<double> gtab;
-  if (C > 0 && !h->opt_on(OPT_ASTAR_NO_GRID)) {
-    int nc = 1;
-    while (nc < C && rc[4 * (size_t)nc + 1] == rc[1] && rc[4 * (size_t)nc + 3] == rc[3]) nc++;
-    if (C % nc == 0) {
-      const int nr = C / nc;
-      gtab.resize(2 * (size_t)nc + 2 * (size_t)nr);
-      double* X0 = gtab.data(); double* X1 = X0 + nc; double* Y0 = X1 + nc; double* Y1 = Y0 + nr;
-      for (int c = 0; c < nc; c++) { X0[c] = rc[4 * (size_t)c]; X1[c] = rc[4 * (size_t)c + 2]; }
-      for (int r = 0; r < nr; r++) { Y0[r] = rc[4 * (size_t)r * nc + 1]; Y1[r] = rc[4 * (size_t)r * nc + 3]; }
-      bool ok = true;
-      for (int r = 0; r < nr && ok; r++)
-        for (int c = 0; c < nc && ok; c++) {
-          const double* q = &rc[4 * ((size_t)r * nc + c)];
-          ok = q[0] == X0[c] && q[2] == X1[c] && q[1] == Y0[r] && q[3] == Y1[r];
-        }
-      auto axis_ok = [](const double* lo, const double* hi, int n) {
-        double scale = 1.0;
-        for (int i = 0; i < n; i++) {
-          if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) return false;
-          scale = std::fmax(scale, std::fmax(std::fabs(lo[i]), std::fabs(hi[i])));
-        }
-        for (int i = 0; i < n; i++) {
-          if (!(hi[i] - lo[i] >= 1e-6 * scale)) return false;
-          if (i + 1 < n && !(lo[i + 1] >= hi[i])) return false;
-        }
-        return true;
-      };
-      if (ok && axis_ok(X0, X1, nc) && axis_ok(Y0, Y1, nr)) { g_ncol = nc; g_nrow = nr; }
-    }
-  }
-  int rc_;
-  if (g_ncol > 0 && (rc_ = upload(h, S.gridtab, gtab.data(), gtab.size()))) return rc_;
-  if ((rc_ = upload(h, S.ox, ox.data(), ox.size()))) return rc_;
-  if ((rc_ = upload(h, S.oy, oy.data(), oy.size()))) return rc_;
-  if ((rc_ = upload(h, S.ot, ot.data(), ot.size()))) return rc_;
-  if ((rc_ = upload(h, S.hab, hab.data(), hab.size()))) return rc_;
-  if ((rc_ = upload(h, S.poly, h->w_poly.data(), h->w_poly.size()))) return rc_;
-  if ((rc_ = upload(h, S.bins, h->w_bins.data(), h->w_bins.size()))) return rc_;
-  if ((rc_ = upload(h, S.rcells, rc.data(), rc.size()))) return rc_;
-  if ((rc_ = upload(h, S.prob, h->w_prob.data(), h->w_prob.size()))) return rc_;
-  if ((rc_ = upload(h, S.topn, topn.data(), topn.size()))) return rc_;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const auvp::AstarWorldTables t = auvp::build_astar_world_tables(h->w_obst.data(), O, h->w_hab.data(), H, h->w_poly.data(), V, T, h->w_cells.data(), C,
+                                                                  h->w_prob.data(), h->opt_on(OPT_ASTAR_NO_GRID));
+  // (no grid: no table, and the buffer is not touched)
+  int rc = upload_tables(h, {{S.gridtab, t.gtab}, {S.ox, t.ox}, {S.oy, t.oy}, {S.ot, t.ot}, {S.hab, t.hab}, {S.poly, h->w_poly}, {S.bins, h->w_bins},
+                             {S.rcells, t.rc}, {S.prob, h->w_prob}, {S.topn, t.topn}});
+  if (rc != AUVP_OK) return rc;
   auvp::AstarWorldDev& W = S.W;
   W.n_obstacles = O; W.n_habitats = H; W.n_poly = V; W.n_bins = T; W.n_cells = C;
   W.ox = S.ox.as<double>(); W.oy = S.oy.as<double>(); W.ot = S.ot.as<double>(); W.hab = S.hab.as<double>();
   W.poly = S.poly.as<double>(); W.bins = S.bins.as<double>(); W.rcells = S.rcells.as<double>();
   W.prob = S.prob.as<double>(); W.topn = S.topn.as<double>();
-  W.g_ncol = g_ncol; W.g_nrow = g_nrow;
+  W.g_ncol = t.g_ncol; W.g_nrow = t.g_nrow;
   W.gx0 = W.gx1 = W.gy0 = W.gy1 = nullptr;
-  W.g_inv_dx = W.g_inv_dy = 0.0;
-  W.g_x1_0 = W.g_y1_0 = 0.0;
-  if (g_ncol > 0) {
-    W.gx0 = S.gridtab.as<double>(); W.gx1 = W.gx0 + g_ncol; W.gy0 = W.gx1 + g_ncol; W.gy1 = W.gy0 + g_nrow;
-    const double* X1 = gtab.data() + g_ncol; const double* Y1 = gtab.data() + 2 * (size_t)g_ncol + g_nrow;
-    W.g_x1_0 = X1[0]; W.g_y1_0 = Y1[0];
-    W.g_inv_dx = g_ncol > 1 ? (g_ncol - 1) / (X1[g_ncol - 1] - X1[0]) : 0.0;
-    W.g_inv_dy = g_nrow > 1 ? (g_nrow - 1) / (Y1[g_nrow - 1] - Y1[0]) : 0.0;
-  }
-  W.cx = V > 0 ? sx / (3.0 * a2) : 0.0;
-  W.cy = V > 0 ? sy / (3.0 * a2) : 0.0;
+  if (t.g_ncol > 0) { W.gx0 = S.gridtab.as<double>(); W.gx1 = W.gx0 + t.g_ncol; W.gy0 = W.gx1 + t.g_ncol; W.gy1 = W.gy0 + t.g_nrow; }
+  W.g_x1_0 = t.g_x1_0; W.g_y1_0 = t.g_y1_0; W.g_inv_dx = t.g_inv_dx; W.g_inv_dy = t.g_inv_dy;
+  W.cx = t.cx; W.cy = t.cy;
   S.world_version = h->world_version;
   return AUVP_OK;
 }
@@ -246,13 +181,7 @@ int astar_batch_run(auvp_handle* h, int32_t E, const double* starts, const doubl
       if (S.visited_set_for != (long long)entries) return fail(h, AUVP_ERR_STATE, "auvp_astar_set_visited not called for this batch shape");
     } else {
       // a fresh visited array = a new epoch; the words are only cleared when the buffer is new or the tag wraps
-      // (255: tests/test_gpu_epoch_wrap.py runs 260 batches on one handle and counts on the wrap falling at batch 256)
-      if (S.cellinfo_clean_cap != S.cellinfo.cap || S.epoch >= 255u) {
-        HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
-        S.cellinfo_clean_cap = S.cellinfo.cap;
-        S.epoch = 0;
-      }
-      S.epoch++;
+      if ((rc = astar_next_epoch(h, S, S.cellinfo_clean_cap != S.cellinfo.cap))) return rc;
     }
     S.visited_set_for = -1;
     P.epoch = S.epoch;
@@ -305,12 +234,7 @@ int astar_batch_run(auvp_handle* h, int32_t E, const double* starts, const doubl
     if (n > 0 && h->opt_flag(OPT_PIPE_FALLBACK, true)) {
       h->pipe_fallback_last = n;
       h->pipe_fallback_total += n;
-      // (255 as above; tests/test_gpu_astar_pair.py::test_the_redo_clears_the_visited_words_at_the_tag_wrap gives up on batch 255)
-      if (S.epoch >= 255u) {
-        HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
-        S.epoch = 0;
-      }
-      S.epoch++;
+      if ((rc = astar_next_epoch(h, S, false))) return rc;
       P.epoch = S.epoch;
       pair = false;
       HIPCHK(h, launch3(false));  // (with sets: the one-wavefront sets form, every instance on its own table again)
@@ -413,13 +337,8 @@ int auvp_astar_set_visited(auvp_handle* h, int32_t E, int32_t variant, const uin
   HIPCHK(h, hipSetDevice(h->device));
   const size_t entries = (size_t)E * (variant == 2 ? 550 : 600) * 600;
   HIPCHK(h, S.cellinfo.reserve(entries * sizeof(uint32_t)));
-  // (255 as in auvp_astar_batch: tests/test_gpu_epoch_wrap.py, whose bitmaps go in on either side of the wrap)
-  if (S.cellinfo_clean_cap != S.cellinfo.cap || S.epoch >= 255u) {
-    HIPCHK(h, hipMemsetAsync(S.cellinfo.p, 0, S.cellinfo.cap, h->stream));
-    S.cellinfo_clean_cap = S.cellinfo.cap;
-    S.epoch = 0;
-  }
-  S.epoch++;
+  // (as auvp_astar_batch: tests/test_gpu_epoch_wrap.py puts bitmaps in on either side of the wrap)
+  if (int rc = astar_next_epoch(h, S, S.cellinfo_clean_cap != S.cellinfo.cap)) return rc;
   std::vector<uint32_t> words(entries);
   const uint32_t tag = S.epoch << 24;
   for (size_t i = 0; i < entries; i++) words[i] = bitmap[i] ? (tag | 0x10000u) : 0u;

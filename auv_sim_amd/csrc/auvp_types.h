@@ -134,6 +134,14 @@ struct RrtSummary {  // must match auvp_rrt_summary in include/auvplan.h
 // node: they are read one at a time by the whole wave); path points are 48-B records, a node's run contiguous.
 #define AUVP_BIN_HEAD 128
 
+// the nearest-neighbour scan's block (rrt_explore_kernel.h: nn_closest reads RRT_NN_UNROLL entries per lane at a time) and the
+// episode stride of the x,y mirror it reads: cap_nodes rounded up to whole blocks
+constexpr int RRT_NN_UNROLL = 8;
+constexpr int RRT_NN_BLOCK = 64 * RRT_NN_UNROLL;
+constexpr long long rrt_nn_stride(int cap_nodes) {
+  return ((long long)cap_nodes + RRT_NN_BLOCK - 1) / RRT_NN_BLOCK * RRT_NN_BLOCK;
+}
+
 struct RrtBuffers {
   int32_t cap_nodes, cap_points, bin_cap, cap_leaves;
   // [E][cap_nodes][8]  x, y, theta, traj_t, length, S, tv, hab   (64 B per node); S/tv/hab: see below

@@ -29,6 +29,7 @@
 #include "planner_goal_arc.h"
 #include "planner_pipe_kernel.h"
 #include "launch_plan.h"  // (behind every kernel header whose LDS plan and limits the choice reads)
+#include "batch_plan.h"   // (what a batch needs in HBM, the stream's rules, the epoch tags: pure as well)
 #include "world_tables.h"
 #include "forecast_place.h"
 
@@ -87,16 +88,7 @@ struct auvp_handle {
   double last_expand_ms = 0.0, last_leaf_ms = 0.0, last_stream_ms = 0.0;
   long long last_stream_len = 0;  // numbers per episode the last pass generated ahead (0: none)
   int last_stream_mirror = -1;    // the ring's form in the last pass's rrt_rows_stream_kernel: 1 mirrored, 0 masked (-1: another kernel ran)
-  // what complete passes of RRT.exploring drew, per parameter block (the last four): the most random() numbers of one episode and
-  // the largest batch seen (the length of the next batch's pre-generated stream: rrt_run_pass)
-  struct Drawn { RrtParamsDev P{}; long long most = 0; int E = 0; unsigned long long used = 0; bool valid = false; };
-  Drawn drawn[4];
-  unsigned long long drawn_clock = 0;
-  Drawn* drawn_find(const RrtParamsDev& P) {
-    for (Drawn& d : drawn)
-      if (d.valid && memcmp(&d.P, &P, sizeof P) == 0) return &d;
-    return nullptr;
-  }
+  DrawnMemory drawn;  // what complete passes of RRT.exploring drew (batch_plan.h): the length of the next batch's stream
   int last_rows = 0;
   const char* last_rrt_kernel = "";
   std::string err;
@@ -459,30 +451,38 @@ int auvp_rrt_prepare_episodes(auvp_handle* h, int32_t E, const double* init, con
   if (!(p->bin_interval > 0)) return fail(h, AUVP_ERR_ARG, "bin_interval <= 0");
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
   const int H = h->W.n_habitats;
-  const uint64_t all = H >= 64 ? ~0ull : ((1ull << H) - 1ull);
-  std::vector<RrtEpisodeLimDev> lim((size_t)E);
-  std::vector<int32_t> ks((size_t)E);
-  for (int e = 0; e < E; e++) {
-    const double t = episodes[e].max_traj_time;
-    if (!(t > 0.0 && t <= p->max_traj_time))
-      return fail(h, AUVP_ERR_ARG, "episode %d: max_traj_time %g outside (0, %g]", e, t, p->max_traj_time);
-    if (episodes[e].habitat_keep & ~all) return fail(h, AUVP_ERR_ARG, "episode %d: habitat_keep names habitats >= %d", e, H);
-    lim[e].max_traj_time = t;
-    lim[e].keep = episodes[e].habitat_keep;
-    lim[e].K = ks[e] = (int)std::ceil(t / p->bin_interval);  // <= the cap's K (ceil is monotone)
-    lim[e]._pad = 0;
+  RrtEpisodeLimits lims = rrt_episode_limits(*p, H, episodes, E);
+  if (const int e = lims.bad_episode; e >= 0) {
+    if (lims.why == RRT_EPISODE_HORIZON)
+      return fail(h, AUVP_ERR_ARG, "episode %d: max_traj_time %g outside (0, %g]", e, episodes[e].max_traj_time, p->max_traj_time);
+    if (lims.why == RRT_EPISODE_KEEP) return fail(h, AUVP_ERR_ARG, "episode %d: habitat_keep names habitats >= %d", e, H);
+    return fail(h, AUVP_ERR_ARG, "episode %d: max_traj_time / bin_interval = %g does not fit an int", e, episodes[e].max_traj_time / p->bin_interval);
   }
   int rc = rrt_prepare_impl(h, E, init, seeds, seeds ? nullptr : mt, seeds ? nullptr : mt_index, p, flags, true);
   if (rc != AUVP_OK) return rc;
   // the batch is prepared only with its limits on the device: a failed upload leaves nothing a later auvp_rrt_run could launch
   // (it would run every episode at the cap's horizon with the whole habitat list)
   h->prepared = false;
-  if ((rc = upload(h, h->d_lim, lim.data(), lim.size()))) return rc;
+  if ((rc = upload(h, h->d_lim, lims.lim.data(), lims.lim.size()))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->prepared = true;
   h->lim = true;
-  h->lim_K.swap(ks);
+  h->lim_K.swap(lims.K);
   return AUVP_OK;
+}
+
+// the message of a batch the plan refuses (batch_plan.h: one status per refusal)
+static int rrt_refuse(auvp_handle* h, const RrtBatchPlan& plan, int n_obstacles) {
+  switch (plan.status) {
+    case RRT_BATCH_BAD_ARGS: return fail(h, AUVP_ERR_ARG, "bad batch arguments");
+    case RRT_BATCH_BAD_PARAMS: return fail(h, AUVP_ERR_ARG, "bad params");
+    case RRT_BATCH_BIN_INTERVAL: return fail(h, AUVP_ERR_ARG, "bin_interval <= 0");
+    case RRT_BATCH_OBSTACLES: return fail(h, AUVP_ERR_ARG, "n_obstacles %d > 1024", n_obstacles);
+    case RRT_BATCH_TOO_MANY_BINS: return fail(h, AUVP_ERR_ARG, "too many time bins (%d)", plan.P.K);
+    case RRT_BATCH_POINTS: return fail(h, AUVP_ERR_ARG, "point capacity too large");
+    case RRT_BATCH_BIN_LISTS: return fail(h, AUVP_ERR_ARG, "time-bin lists too large (K=%d, max_iter=%d)", plan.P.K, plan.P.max_iter);
+    default: return fail(h, AUVP_ERR_ARG, "%s: not a number the batch can be sized from, or too large", plan.field);
+  }
 }
 
 static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const uint64_t* seeds, const uint32_t* states,
@@ -491,103 +491,67 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
   h->lim = false;
   h->grids = false;
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called");
-  if (E <= 0 || !init || !p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
-  if (p->max_iter <= 0 || !(p->freq >= 0) || p->mode < 0 || p->mode > 2) return fail(h, AUVP_ERR_ARG, "bad params");
-  if (p->mode == AUVP_MODE_TIMEBIN && !(p->bin_interval > 0)) return fail(h, AUVP_ERR_ARG, "bin_interval <= 0");
-  if (h->W.n_obstacles > 16 * 64) return fail(h, AUVP_ERR_ARG, "n_obstacles %d > 1024", h->W.n_obstacles);
+  if (!init || !p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
+  // every capacity and byte count of the batch, or why there is none (batch_plan.h): nothing of the handle changes on a refusal
+  RrtBatchIn in;
+  in.E = E; in.p = *p; in.flags = flags; in.n_obstacles = h->W.n_obstacles;
+  const RrtBatchPlan plan = rrt_batch_plan(in);
+  if (plan.status != RRT_BATCH_OK) return rrt_refuse(h, plan, h->W.n_obstacles);
   HIPCHK(h, hipSetDevice(h->device));
-  RrtParamsDev& P = h->P;
-  P.dist_to_end = p->dist_to_end; P.diff_max = p->diff_max; P.freq = p->freq; P.min_dist = p->min_dist;
-  P.bin_interval = p->bin_interval; P.v = p->v; P.max_traj_time = p->max_traj_time; P.max_plan_time = p->max_plan_time;
-  P.w[0] = p->w[0]; P.w[1] = p->w[1]; P.w[2] = p->w[2];
-  P.mode = p->mode; P.max_iter = p->max_iter; P.flags = flags;
-  P.inv_bin_interval = p->bin_interval > 0 ? 1.0 / p->bin_interval : 0.0;
-  P.K = p->mode == AUVP_MODE_TIMEBIN ? (int)std::ceil(p->max_traj_time / p->bin_interval) : 0;
-  if (P.K > 1 << 20) return fail(h, AUVP_ERR_ARG, "too many time bins (%d)", P.K);
-  const int nfreq = (int)std::floor(p->freq);
-  h->max_pts = nfreq + 2;
+  const RrtParamsDev& P = h->P = plan.P;
+  h->max_pts = plan.max_pts;
   // the pre-generated random stream of earlier batches (tens of GB, rrt_run_pass) stays with the handle while the batches are of
   // its kind -- a caller alternating between worlds does not pay a hipMalloc per call -- and goes back before a batch of
   // another kind reserves its own buffers
-  if (h->d_stream.p && (lim || !(P.mode == 0 && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true) &&
-                                 h->opt_flag(OPT_ROWS, rrt_rows_by_size(E, h->n_cu)))))
-    h->d_stream.release();
-  RrtBuffers& B = h->B;
-  B.cap_nodes = p->max_iter + 1;
-  // Path-point budget.  A steer appends at most n = floor(uniform(0, freq)) points (:258-262) and only an accepted one
-  // keeps them, so an episode's total is dominated by a sum of max_iter independent draws of n: mean <= freq/2 each,
-  // standard deviation <= freq/sqrt(12).  The default budget is that mean plus EIGHT standard deviations of the sum
-  // (exceeded with probability < 1e-15 per episode; the bench world uses 68 % of it), never more than the worst case;
-  // points_per_iter overrides it (freq + 1 = the worst case).  Running out is AUVP_ERR_CAPACITY, never a truncation.
-  const double n_it = (double)p->max_iter;
-  const double worst = n_it * (nfreq > 1 ? nfreq : 1);
-  double cp = p->points_per_iter > 0 ? std::ceil(p->points_per_iter * n_it)
-                                     : std::ceil(std::fmin(worst, 0.5 * p->freq * n_it + 8.0 * p->freq / std::sqrt(12.0) * std::sqrt(n_it)));
-  cp += nfreq + 64;
-  if (cp > 2.0e9) return fail(h, AUVP_ERR_ARG, "point capacity too large");
-  B.cap_points = (int32_t)cp;
-  B.bin_cap = P.K > 0 ? B.cap_nodes : 1;
-  // chunked member lists: AUVP_BIN_HEAD direct-mapped members per bin, the rest in 64-entry chunks (auvp_types.h)
-  const bool chunks = B.bin_cap > AUVP_BIN_HEAD;
-  B.bin_over = chunks ? (B.cap_nodes + 63) / 64 + P.K + 1 : 0;
-  B.bin_slots = chunks ? (B.bin_cap - AUVP_BIN_HEAD + 63) / 64 : 0;
-  B.bin_stride = (long long)(P.K + 1) * AUVP_BIN_HEAD + (long long)B.bin_over * 64 + (long long)B.bin_slots * (P.K + 1);
-  if (B.bin_stride >= (1ll << 31)) return fail(h, AUVP_ERR_ARG, "time-bin lists too large (K=%d, max_iter=%d)", P.K, p->max_iter);
-  B.cap_leaves = (flags & AUVP_FLAG_LEAF_LOG) ? B.cap_nodes : 1;
-  const size_t cn = (size_t)E * B.cap_nodes, cpnt = (size_t)E * B.cap_points;
-  HIPCHK(h, h->d_nodes_f.reserve(cn * 8 * sizeof(double)));
-  HIPCHK(h, h->d_nodes_i.reserve(cn * 4 * sizeof(int32_t)));
-  HIPCHK(h, h->d_points.reserve(cpnt * 6 * sizeof(double)));
-  HIPCHK(h, h->d_bin_items.reserve((size_t)E * (size_t)B.bin_stride * sizeof(int32_t)));
-  HIPCHK(h, h->d_bin_count.reserve((size_t)E * (P.K + 1) * sizeof(int32_t)));
-  HIPCHK(h, h->d_summary.reserve((size_t)E * sizeof(RrtSummary)));
-  HIPCHK(h, h->d_node_c.reserve(cn * 8 * sizeof(int32_t)));
-  HIPCHK(h, h->d_node_q.reserve(cn));
+  if (h->d_stream.p && !rrt_stream_keeps(h->opt, P.mode, P.max_iter, lim, rrt_rows_wanted(h->opt, E, h->n_cu))) h->d_stream.release();
+  RrtBuffers& B = h->B = plan.B;  // (the capacities; every pointer null until its buffer is reserved below)
+  const RrtBatchBytes& bytes = plan.bytes;
+  HIPCHK(h, h->d_nodes_f.reserve(bytes.nodes_f));
+  HIPCHK(h, h->d_nodes_i.reserve(bytes.nodes_i));
+  HIPCHK(h, h->d_points.reserve(bytes.points));
+  HIPCHK(h, h->d_bin_items.reserve(bytes.bin_items));
+  HIPCHK(h, h->d_bin_count.reserve(bytes.bin_count));
+  HIPCHK(h, h->d_summary.reserve(bytes.summary));
+  HIPCHK(h, h->d_node_c.reserve(bytes.node_c));
+  HIPCHK(h, h->d_node_q.reserve(bytes.node_q));
   B.node_f = h->d_nodes_f.as<double>();
   B.node_i = h->d_nodes_i.as<int32_t>();
   B.points = h->d_points.as<double>();
   B.node_c = h->d_node_c.as<int32_t>();
   B.node_q = h->d_node_q.as<uint8_t>();
   // nearest-neighbour sampling scans a contiguous x,y mirror of the nodes (auvp_types.h); the other modes never touch it
-  B.node_xy = nullptr;
-  B.xy_stride = 0;
-  if (p->mode == AUVP_MODE_NN) {
-    B.xy_stride = rrt_nn_stride(B.cap_nodes);
-    HIPCHK(h, h->d_node_xy.reserve((size_t)E * (size_t)B.xy_stride * 2 * sizeof(double)));
+  if (P.mode == AUVP_MODE_NN) {
+    HIPCHK(h, h->d_node_xy.reserve(bytes.node_xy));
     B.node_xy = h->d_node_xy.as<double>();
   }
   B.bin_items = h->d_bin_items.as<int32_t>();
   B.bin_count = h->d_bin_count.as<int32_t>();
   B.summary = h->d_summary.as<RrtSummary>();
-  B.it_parent = nullptr; B.it_accepted = nullptr; B.it_npath = nullptr; B.leaf_cost = nullptr; B.leaf_iter = nullptr;
   if (flags & AUVP_FLAG_ITER_LOG) {
-    const size_t n = (size_t)E * p->max_iter;
-    HIPCHK(h, h->d_itlog_i.reserve(n * 2 * sizeof(int32_t)));
-    HIPCHK(h, h->d_itlog_b.reserve(n));
+    HIPCHK(h, h->d_itlog_i.reserve(bytes.itlog_i));
+    HIPCHK(h, h->d_itlog_b.reserve(bytes.itlog_b));
     B.it_parent = h->d_itlog_i.as<int32_t>();
-    B.it_npath = B.it_parent + n;
+    B.it_npath = B.it_parent + plan.itlog_n;
     B.it_accepted = h->d_itlog_b.as<int8_t>();
   }
   if (flags & AUVP_FLAG_LEAF_LOG) {
-    HIPCHK(h, h->d_leaf_c.reserve((size_t)E * B.cap_leaves * 6 * sizeof(double)));
-    HIPCHK(h, h->d_leaf_i.reserve((size_t)E * B.cap_leaves * sizeof(int32_t)));
+    HIPCHK(h, h->d_leaf_c.reserve(bytes.leaf_c));
+    HIPCHK(h, h->d_leaf_i.reserve(bytes.leaf_i));
     B.leaf_cost = h->d_leaf_c.as<double>();
     B.leaf_iter = h->d_leaf_i.as<int32_t>();
   }
-  B.phase_clocks = nullptr;
-  HIPCHK(h, h->d_leaf_stats.reserve(8 * sizeof(unsigned long long)));
+  HIPCHK(h, h->d_leaf_stats.reserve(bytes.leaf_stats));
   B.leaf_stats = h->d_leaf_stats.as<unsigned long long>();
   B.pipe_fail = h->pipe_fail_dev;
   if (flags & AUVP_FLAG_PHASE_CLOCKS) {
-    HIPCHK(h, h->d_phase.reserve((size_t)E * 5 * sizeof(unsigned long long)));
-    HIPCHK(h, hipMemsetAsync(h->d_phase.p, 0, (size_t)E * 5 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, h->d_phase.reserve(bytes.phase));
+    HIPCHK(h, hipMemsetAsync(h->d_phase.p, 0, bytes.phase, h->stream));
     B.phase_clocks = h->d_phase.as<unsigned long long>();
   }
   // seeds -> MT states, once per batch: random.seed(seeds[e]) on the device (auvp_seed.h)
   int rc;
-  B.mt_index = nullptr;
   if (seeds) {
-    HIPCHK(h, h->d_mt.reserve((size_t)E * 624 * sizeof(uint32_t)));
+    HIPCHK(h, h->d_mt.reserve(bytes.mt));
     if ((rc = upload(h, h->d_seeds, seeds, (size_t)E))) return rc;
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(auvp::mt_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   auvp::MT_SEED_LDS));
@@ -614,19 +578,15 @@ static int rrt_prepare_impl(auvp_handle* h, int32_t E, const double* init, const
 }  // extern "C"
 
 // 1: the buffer of the pre-generated random stream (rrt_stream_kernel.h) holds `bytes`; 0: it does not fit the free memory beside
-// a 4 GB margin (or the allocation failed).  A buffer that
-// has to grow is taken 6 % larger than asked for: the length follows the busiest episode seen so far, which creeps up by a few
-// parts in a thousand from batch to batch, and every re-allocation of tens of GB is a second or two of hipFree + hipMalloc.
+// a 4 GB margin (or the allocation failed).  How much a buffer that has to grow takes: rrt_stream_want_bytes (batch_plan.h).
 // *grew: an allocation happened (the caller re-records its start event: nothing has been launched yet)
 static int rrt_stream_reserve(auvp_handle* h, size_t bytes, bool* grew = nullptr) {
   if (grew) *grew = false;
   if (h->d_stream.cap >= bytes) return 1;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  const size_t have = free_b + h->d_stream.cap, margin = (size_t)4 << 30;
-  const size_t padded = bytes + bytes / 16;
-  const size_t want = have >= padded + margin ? padded : bytes;
-  if (have < want + margin || h->d_stream.reserve(want) != hipSuccess) {
+  const size_t want = rrt_stream_want_bytes(free_b, h->d_stream.cap, bytes);
+  if (!want || h->d_stream.reserve(want) != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }
@@ -708,25 +668,11 @@ static void rrt_record_drawn(auvp_handle* h, const RrtLaunchPlan& plan) {
   unsigned long long d32 = 0;
   memcpy(&d32, h->pipe_fail_host + 2, sizeof d32);
   if (d32 == 0) return;
-  // (the most seen with these parameters: worlds that alternate between a little more and a little less do not make every
-  // other batch run past its stream; a parameter block not seen before takes the slot used longest ago)
-  auvp_handle::Drawn* d = h->drawn_find(P);
-  const long long now = (long long)((d32 + 1) / 2);
-  if (!d) {
-    d = &h->drawn[0];
-    for (auvp_handle::Drawn& x : h->drawn)
-      if (!x.valid || (d->valid && x.used < d->used)) d = &x;
-    *d = auvp_handle::Drawn{};
-    d->P = P;
-    d->valid = true;
-  }
-  d->most = d->most > now ? d->most : now;
-  d->E = d->E > h->E ? d->E : h->E;
-  d->used = ++h->drawn_clock;
+  const DrawnMemory::Slot& d = h->drawn.record(P, (long long)((d32 + 1) / 2), h->E);
   // the next batch with these parameters will want its stream: the buffer is taken NOW, in the call that found
   // out (tens of GB: a second of hipMalloc that a later, timed call would pay otherwise)
-  if (plan.kind == RRT_ROWS && P.max_iter >= 1000 && h->opt_flag(OPT_ROWS_STREAM, true)) {
-    const long long cap_next = rrt_stream_len(h->opt, d->most, P.max_iter);
+  if (rrt_stream_keeps(h->opt, P.mode, P.max_iter, h->lim, plan.kind == RRT_ROWS)) {
+    const long long cap_next = rrt_stream_len(h->opt, d.most, P.max_iter);
     if (cap_next <= 0x7fffffffll) (void)rrt_stream_reserve(h, (size_t)h->E * (size_t)cap_next * sizeof(double));
   }
 }
@@ -760,7 +706,7 @@ static int rrt_run_pass(auvp_handle* h, bool one_wave_only, bool no_stream = fal
   in.max_pts = h->max_pts;
   in.O = h->W.n_obstacles; in.H = h->W.n_habitats; in.V = h->W.n_poly; in.T = h->W.n_bins; in.obst_area = h->obst_area;
   in.lim = h->lim; in.one_wave_only = one_wave_only; in.no_stream = no_stream;
-  if (const auvp_handle::Drawn* seen = h->drawn_find(P)) { in.seen_most = seen->most; in.seen_E = seen->E; }
+  if (const DrawnMemory::Slot* seen = h->drawn.find(P)) { in.seen_most = seen->most; in.seen_E = seen->E; }
   RrtLaunchPlan plan = rrt_choose_launch(in, h->opt);
   h->last_stream_mirror = -1;
   h->last_stream_ms = 0.0;

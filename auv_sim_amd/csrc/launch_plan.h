@@ -10,44 +10,9 @@
 #ifndef AUVP_LAUNCH_PLAN_H
 #define AUVP_LAUNCH_PLAN_H
 #include <cmath>
-#include <cstring>
 #include <type_traits>
 
-// Tuning / diagnostic options of a handle (auvp_set_option, include/auvplan.h).  Every kernel choice the host makes has a
-// measured default ("auto": the option is unset); an option forces it.  The environment variable AUVP_<NAME> gives an
-// option its initial value ONCE, when the handle is created -- no launch path reads the environment.
-#define AUVP_OPTIONS(X)                                                                                                     \
-  X(ROWS) X(DUO) X(TRIO) X(QUAD) X(TIGHT_CULL) X(NN_EXACT) X(LEAF_SWEEP_ALL) X(NO_HABITAT_GRID) X(RG_MAX_ENTRIES)           \
-  X(NO_GRID_INDEX) X(PRRT_LAT) X(PRRT_PIPE) X(PRRT_OBST_LDS) X(PRRT_NEXT_LDS) X(PRRT_ROWS) X(ASTAR_NO_GRID)                 \
-  X(ASTAR_NO_LIST) X(ASTAR_PAIR) X(SOG_TILE) X(PIPE_FALLBACK) X(PRRT_PIPE_DRAW) X(PRRT_BUCKET_LDS) X(ROWS_STREAM)           \
-  X(ROWS_STREAM_CAP) X(ROWS_STREAM_WAVES) X(ROWS_WG_WAVES) X(ROWS_STREAM_MIRROR) X(PRRT_ROWS_GRID)          \
-  X(SF_WIDE_MIN) X(SF_WIDE_BLOCK)
-enum AuvpOpt {
-#define AUVP_OPT_ENUM(n) OPT_##n,
-  AUVP_OPTIONS(AUVP_OPT_ENUM)
-#undef AUVP_OPT_ENUM
-  OPT_COUNT
-};
-static const char* const AUVP_OPT_NAMES[OPT_COUNT] = {
-#define AUVP_OPT_NAME(n) #n,
-  AUVP_OPTIONS(AUVP_OPT_NAME)
-#undef AUVP_OPT_NAME
-};
-// the option called `name` (without the AUVP_ prefix); -1: there is none
-inline int auvp_option_index(const char* name) {
-  for (int k = 0; k < OPT_COUNT; k++)
-    if (!strcmp(name, AUVP_OPT_NAMES[k])) return k;
-  return -1;
-}
-
-struct OptionView {
-  bool opt_has[OPT_COUNT] = {};
-  long long opt_val[OPT_COUNT] = {};
-  // option K as a yes / no choice: its value when set, `dflt` (the measured heuristic) otherwise
-  bool opt_flag(int k, bool dflt) const { return opt_has[k] ? opt_val[k] != 0 : dflt; }
-  bool opt_on(int k) const { return opt_has[k] && opt_val[k] != 0; }
-  long long opt_num(int k, long long dflt) const { return opt_has[k] ? opt_val[k] : dflt; }
-};
+#include "launch_options.h"  // (the options, OptionView, rrt_rows_by_size, rrt_stream_len: free of the kernel headers)
 
 namespace auvp {
 
@@ -115,20 +80,6 @@ struct RrtLaunchPlan {
   bool rows() const { return kind == RRT_ROWS || kind == RRT_ROWS_STREAM; }
 };
 
-// "does this batch get a four-episode kernel by its size": above 18 episodes per CU (see rrt_choose_launch; rrt_prepare_impl
-// keeps the stream buffer by the same figure)
-constexpr int RRT_ROWS_EP_PER_CU = 18;
-inline bool rrt_rows_by_size(int E, int n_cu) { return E > RRT_ROWS_EP_PER_CU * n_cu; }
-
-// The pre-generated random stream of a batch (rrt_stream_kernel.h): its length in numbers per episode -- from what the previous
-// batches with the same parameters drew (seen_most > 0), else 46.5 per iteration + 4 096
-inline long long rrt_stream_len(const OptionView& opt, long long seen_most, int max_iter) {
-  const long long guess = seen_most > 0 ? seen_most + seen_most * 3 / 100 + 1024 : (long long)(46.5 * (double)max_iter) + 4096;
-  long long cap = opt.opt_num(OPT_ROWS_STREAM_CAP, guess);
-  cap = cap < 64 ? 64 : cap;
-  return (cap + 63) / 64 * 64;
-}
-
 inline RrtLaunchPlan rrt_choose_launch(const RrtLaunchIn& in, const OptionView& opt) {
   RrtLaunchPlan p;
   const int E = in.E, n_cu = in.n_cu, O = in.O;
@@ -166,7 +117,7 @@ inline RrtLaunchPlan rrt_choose_launch(const RrtLaunchIn& in, const OptionView& 
   // (a batch with per-episode limits runs rrt_explore_lim_kernel, whatever the options say)
   const bool rows_ok = !in.lim && in.mode == 0 && !iter_log && nfreq <= RW_MAX_FREQ && O <= RW_MAX_OBST && in.max_iter < 65534 &&
                        rp.total <= LDS_LIMIT;
-  const bool use_rows = rows_ok && opt.opt_flag(OPT_ROWS, rrt_rows_by_size(E, n_cu));
+  const bool use_rows = rows_ok && rrt_rows_wanted(opt, E, n_cu);
   // latency runs (at most four episodes per CU: one episode, config 2's 1 024 replicas): two wavefronts per episode
   // (rrt_duo_kernel.h).  Option DUO = 1 / 0 forces it on (limits permitting) / off.
   const bool duo_ok = !in.lim && in.mode == 0 && !diag && nfreq <= DUO_MAX_FREQ && nfreq >= 1 && O <= 256 && in.max_pts <= 64;

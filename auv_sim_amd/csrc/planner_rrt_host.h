@@ -4,6 +4,8 @@
 #define AUVP_PLANNER_RRT_HOST_H
 
 static_assert(sizeof(auvp_prrt_summary) == sizeof(auvp::PrrtSummary), "prrt summary layout");
+static_assert(sizeof(auvp::PrrtNode) == auvp::PRRT_NODE_BYTES && sizeof(int2) == auvp::PRRT_BUCKET_BYTES &&
+              sizeof(auvp::PrrtSummary) == auvp::PRRT_SUMMARY_BYTES, "the record sizes batch_plan.h counts bytes by");
 
 namespace {
 
@@ -19,6 +21,7 @@ struct PrrtState {
   int bucket_epoch = 0;
   void* bucket_alloc = nullptr;
   size_t bucket_alloc_bytes = 0;
+  size_t bucket_bytes = 0;  // of the configured batch's table (the plan's figure)
   // work counter of the four-episodes-per-wavefront kernel (planner_rows_kernel.h).  It is never reset between launches: a
   // launch hands out ids counter - work_base, and every one of its rows ends with exactly one pull that finds no episode, so
   // the next launch's base is known on the host (no fill launch per plan / step)
@@ -167,46 +170,49 @@ extern "C" {
 // the starts, goals and generator states come from)
 static int prrt_configure(auvp_handle* h, PrrtState& S, int32_t E, const auvp_prrt_params* p, int32_t flags) {
   if (!h->have_world) return fail(h, AUVP_ERR_STATE, "auvp_world_set not called (obstacle list)");
-  if (E <= 0 || !p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
-  if (h->W.n_obstacles > 16 * 64) return fail(h, AUVP_ERR_ARG, "n_obstacles %d > 1024", h->W.n_obstacles);
-  const int ics = (int)p->cell_side_length;
-  if (ics <= 0 || p->subsections <= 0 || p->max_step <= 0 || !(p->freq >= 0)) return fail(h, AUVP_ERR_ARG, "bad params");
-  S.ready = false;
-  S.drop_graphs();  // they replay launches on the previous batch's buffers
+  if (!p) return fail(h, AUVP_ERR_ARG, "bad batch arguments");
+  // the grid, every capacity and byte count of the batch, or why there is none (batch_plan.h)
+  auvp::PrrtBatchIn in;
+  in.E = E; in.p = *p; in.flags = flags; in.n_obstacles = h->W.n_obstacles;
+  const auvp::PrrtBatchPlan plan = auvp::prrt_batch_plan(in);
+  // (as ever: a batch that gets as far as its grid gives up the previous one, whatever comes of it)
+  if (plan.status == auvp::PRRT_BATCH_OK || plan.status >= auvp::PRRT_BATCH_EMPTY_GRID) {
+    S.ready = false;
+    S.drop_graphs();  // they replay launches on the previous batch's buffers
+  }
+  switch (plan.status) {
+    case auvp::PRRT_BATCH_OK: break;
+    case auvp::PRRT_BATCH_BAD_ARGS: return fail(h, AUVP_ERR_ARG, "bad batch arguments");
+    case auvp::PRRT_BATCH_OBSTACLES: return fail(h, AUVP_ERR_ARG, "n_obstacles %d > 1024", h->W.n_obstacles);
+    case auvp::PRRT_BATCH_BAD_PARAMS: return fail(h, AUVP_ERR_ARG, "bad params");
+    case auvp::PRRT_BATCH_FIELD: return fail(h, AUVP_ERR_ARG, "%s: not a number the batch can be sized from, or too large", plan.field);
+    case auvp::PRRT_BATCH_EMPTY_GRID: return fail(h, AUVP_ERR_ARG, "empty grid");
+    case auvp::PRRT_BATCH_BUCKETS: return fail(h, AUVP_ERR_ARG, "too many buckets");
+    case auvp::PRRT_BATCH_POINTS: return fail(h, AUVP_ERR_ARG, "point capacity too large");
+    case auvp::PRRT_BATCH_STEPS: return fail(h, AUVP_ERR_ARG, "max_step %d: a bucket's size is kept in 24 bits", p->max_step);
+  }
   auvp::PrrtParamsDev& P = S.P;
   for (int i = 0; i < 4; i++) P.rect[i] = p->rect[i];
   P.exp_rate = p->exp_rate; P.dist_to_end = p->dist_to_end; P.diff_max = p->diff_max; P.freq = p->freq;
   P.cell = p->cell_side_length;
   P.S = p->subsections;
-  // discretize_env (gym_rrt/envs/rrt_dubins.py:77-93): int(height) // int(cell), int(width) // int(cell)
-  P.rows = (int)(p->rect[3] - p->rect[1]) / ics;
-  P.cols = (int)(p->rect[2] - p->rect[0]) / ics;
-  if (P.rows <= 0 || P.cols <= 0) return fail(h, AUVP_ERR_ARG, "empty grid");
-  const double nbd = (double)P.rows * P.cols * P.S;
-  if (nbd > 5.0e7) return fail(h, AUVP_ERR_ARG, "too many buckets");
-  P.n_buckets = (int)nbd;
+  P.rows = plan.rows; P.cols = plan.cols; P.n_buckets = plan.n_buckets;
   P.max_step = p->max_step; P.flags = flags; P.step_mode = 0;
-  P.delta_theta = (double)(2.0 * M_PI) / (double)P.S;  // grid_cell_rrt.py:49
+  P.delta_theta = plan.delta_theta;
   auvp::PrrtBuffers& B = S.B;
-  const int nfreq = (int)std::floor(p->freq);
-  B.cap_nodes = p->max_step + 1;
-  B.max_pts = nfreq + 3;
-  double cp = (double)p->max_step * (double)(nfreq > 0 ? nfreq : 1) + 64;  // every taken sub-arc is stored
-  if (cp > 2.0e9) return fail(h, AUVP_ERR_ARG, "point capacity too large");
-  B.cap_points = (int32_t)cp;
-  if (B.cap_nodes >= (1 << 24)) return fail(h, AUVP_ERR_ARG, "max_step %d: a bucket's size is kept in 24 bits", p->max_step);
-  const size_t cn = (size_t)E * B.cap_nodes;
-  HIPCHK(h, S.nodes.reserve(cn * sizeof(auvp::PrrtNode)));
-  HIPCHK(h, S.node_bucket.reserve(cn * sizeof(int32_t)));
-  HIPCHK(h, S.points.reserve((size_t)E * B.cap_points * 4 * sizeof(double)));
-  HIPCHK(h, S.occupied.reserve(cn * sizeof(int32_t)));
-  HIPCHK(h, S.buckets.reserve((size_t)E * P.n_buckets * sizeof(int2)));
-  HIPCHK(h, S.mt.reserve((size_t)E * 624 * sizeof(uint32_t)));
-  HIPCHK(h, S.rng_state.reserve((size_t)E * 4 * sizeof(int32_t)));
-  HIPCHK(h, S.summary.reserve((size_t)E * sizeof(auvp::PrrtSummary)));
-  HIPCHK(h, S.step_bucket.reserve((size_t)E * sizeof(int32_t)));
-  HIPCHK(h, S.start.reserve((size_t)E * 4 * sizeof(double)));
-  HIPCHK(h, S.goal.reserve((size_t)E * 2 * sizeof(double)));
+  B.cap_nodes = plan.cap_nodes; B.max_pts = plan.max_pts; B.cap_points = plan.cap_points;
+  const auvp::PrrtBatchBytes& bytes = plan.bytes;
+  HIPCHK(h, S.nodes.reserve(bytes.nodes));
+  HIPCHK(h, S.node_bucket.reserve(bytes.node_bucket));
+  HIPCHK(h, S.points.reserve(bytes.points));
+  HIPCHK(h, S.occupied.reserve(bytes.occupied));
+  HIPCHK(h, S.buckets.reserve(S.bucket_bytes = bytes.buckets));
+  HIPCHK(h, S.mt.reserve(bytes.mt));
+  HIPCHK(h, S.rng_state.reserve(bytes.rng_state));
+  HIPCHK(h, S.summary.reserve(bytes.summary));
+  HIPCHK(h, S.step_bucket.reserve(bytes.step_bucket));
+  HIPCHK(h, S.start.reserve(bytes.start));
+  HIPCHK(h, S.goal.reserve(bytes.goal));
   B.nodes = S.nodes.as<auvp::PrrtNode>(); B.node_bucket = S.node_bucket.as<int32_t>();
   B.points = S.points.as<double>(); B.occupied = S.occupied.as<int32_t>(); B.buckets = S.buckets.as<int2>();
   B.mt = S.mt.as<uint32_t>(); B.rng_state = S.rng_state.as<int32_t>(); B.summary = S.summary.as<auvp::PrrtSummary>();
@@ -218,8 +224,8 @@ static int prrt_configure(auvp_handle* h, PrrtState& S, int32_t E, const auvp_pr
   B.pipe_fail = h->pipe_fail_dev; B.redo_mask = nullptr;
   B.env_obs_grid = nullptr; B.env_obs_has = nullptr; B.env_obs_num = nullptr;
   if (flags & AUVP_FLAG_ITER_LOG) {
-    HIPCHK(h, S.st_log.reserve((size_t)E * p->max_step * 8 * sizeof(int32_t)));
-    HIPCHK(h, hipMemsetAsync(S.st_log.p, 0xff, (size_t)E * p->max_step * 8 * sizeof(int32_t), h->stream));
+    HIPCHK(h, S.st_log.reserve(bytes.st_log));
+    HIPCHK(h, hipMemsetAsync(S.st_log.p, 0xff, bytes.st_log, h->stream));
     B.st_log = S.st_log.as<int32_t>();
   }
   // four episodes per wavefront or one: decided here, once per batch (launch_plan.h)
@@ -233,14 +239,13 @@ static int prrt_plant(auvp_handle* h, PrrtState& S, int32_t E) {
   {
     // every bucket of the new batch is empty: a fresh epoch does that without touching the table (E x n_buckets x 8 bytes);
     // the table itself is cleared when its allocation changed or the 8-bit tag wraps (tag 0 is never current)
-    const size_t need = (size_t)E * S.P.n_buckets * sizeof(int2);
-    // (255: tests/test_gpu_epoch_wrap.py runs 260 batches on one handle and counts on the wrap falling at batch 256)
-    if (S.bucket_alloc != S.buckets.p || need > S.bucket_alloc_bytes || S.bucket_epoch >= 255) {
+    const size_t need = S.bucket_bytes;
+    const auvp::EpochTag next = auvp::epoch_tag_next((uint32_t)S.bucket_epoch, S.bucket_alloc != S.buckets.p || need > S.bucket_alloc_bytes);
+    if (next.clear) {
       HIPCHK(h, hipMemsetAsync(S.buckets.p, 0, need, h->stream));
-      S.bucket_alloc = S.buckets.p; S.bucket_alloc_bytes = need; S.bucket_epoch = 0;
+      S.bucket_alloc = S.buckets.p; S.bucket_alloc_bytes = need;
     }
-    S.bucket_epoch++;
-    S.B.bucket_epoch = S.bucket_epoch;
+    S.B.bucket_epoch = S.bucket_epoch = (int)next.tag;
   }
   HIPCHK(h, S.env_done.reserve((size_t)E));
   HIPCHK(h, S.env_err.reserve(2 * sizeof(int32_t)));
@@ -276,14 +281,8 @@ int auvp_prrt_create_batch(auvp_handle* h, int32_t E, const double* starts, cons
                        S.seeds.as<unsigned long long>(), S.B.mt, S.B.rng_state, (int)E);
     HIPCHK(h, hipGetLastError());
   } else {
-    std::vector<uint32_t> words((size_t)E * 624);
-    std::vector<int32_t> rs((size_t)E * 4, 0);
-    for (int e = 0; e < E; e++) {
-      memcpy(words.data() + (size_t)e * 624, mt + (size_t)e * 624, 624 * sizeof(uint32_t));
-      int idx = mt_index[e] < 0 ? 0 : (mt_index[e] > 624 ? 624 : mt_index[e]);
-      rs[4 * (size_t)e] = idx == 624 ? 0 : idx;
-      rs[4 * (size_t)e + 1] = 624 - idx;
-    }
+    const std::vector<uint32_t> words(mt, mt + (size_t)E * 624);
+    const std::vector<int32_t> rs = auvp::prrt_rng_state_rows(mt_index, E);
     if ((rc = upload(h, S.mt, words.data(), words.size()))) return rc;
     if ((rc = upload(h, S.rng_state, rs.data(), rs.size()))) return rc;
   }
@@ -306,12 +305,7 @@ int auvp_prrt_step(auvp_handle* h, const int32_t* bucket_ids, const uint32_t* mt
   int rc;
   if ((rc = upload(h, S.step_bucket, bucket_ids, (size_t)S.E))) return rc;
   if (mt && mt_index) {  // continue an external generator (the global `random` state) for this step
-    std::vector<int32_t> rs((size_t)S.E * 4, 0);
-    for (int e = 0; e < S.E; e++) {
-      int idx = mt_index[e] < 0 ? 0 : (mt_index[e] > 624 ? 624 : mt_index[e]);
-      rs[4 * (size_t)e] = idx == 624 ? 0 : idx;
-      rs[4 * (size_t)e + 1] = 624 - idx;
-    }
+    const std::vector<int32_t> rs = auvp::prrt_rng_state_rows(mt_index, S.E);
     if ((rc = upload(h, S.mt, mt, (size_t)S.E * 624))) return rc;
     if ((rc = upload(h, S.rng_state, rs.data(), rs.size()))) return rc;
   }

@@ -454,11 +454,7 @@ __device__ __forceinline__ void cost_pass(const WorldDev& W, const RrtTables& S,
 // index among them.
 // Otherwise (never observed: it needs two nodes equidistant from the sample to 1e-15) the scan is repeated the reference's
 // way, sqrt per node.  Entries past the tree's end hold +inf: a block is always read whole.
-constexpr int RRT_NN_UNROLL = 8;
-constexpr int RRT_NN_BLOCK = 64 * RRT_NN_UNROLL;
-__host__ __device__ inline long long rrt_nn_stride(int cap_nodes) {
-  return ((long long)cap_nodes + RRT_NN_BLOCK - 1) / RRT_NN_BLOCK * RRT_NN_BLOCK;
-}
+// (RRT_NN_UNROLL, RRT_NN_BLOCK and rrt_nn_stride: auvp_types.h, where the host's sizing reads them too)
 
 // `force_exact` (wave-uniform): take the sqrt-per-node path regardless (tests); `*slow` reports which path ran.
 __device__ __forceinline__ int nn_closest(const double2* __restrict__ xy, int n_nodes, double rx, double ry, bool force_exact = false,
