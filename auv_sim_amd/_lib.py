@@ -875,7 +875,8 @@ class Context:
         self._chk(self.L.auvp_sincos_dev(self.h, len(x), _p(x), _p(s), _p(c)))
         return s, c
 
-    MATH_OPS = {"sincos": 0, "atan2": 1, "pow_e": 2, "div_plain": 3, "sqrt_plain": 4, "hypot": 5, "div": 6, "sqrt": 7}
+    MATH_OPS = {"sincos": 0, "atan2": 1, "pow_e": 2, "div_plain": 3, "sqrt_plain": 4, "hypot": 5, "div": 6, "sqrt": 7,
+                "sincos_sk": 8, "atan2_late": 9, "pow_e_lds": 10, "bearing": 11, "atan": 12}
 
     def math(self, op, a, b=None):
         """auvp_math_dev: one portable elementary function on the device (bit-exactness probe)"""
@@ -883,7 +884,7 @@ class Context:
         b = np.zeros_like(a) if b is None else _f64(b).ravel()
         o0, o1 = np.zeros_like(a), np.zeros_like(a)
         self._chk(self.L.auvp_math_dev(self.h, self.MATH_OPS[op], len(a), _p(a), _p(b), _p(o0), _p(o1)))
-        return (o0, o1) if op == "sincos" else o0
+        return (o0, o1) if op in ("sincos", "sincos_sk") else o0
 
     def theta_chain(self, theta0, phi):
         """auvp_theta_chain_dev: rows_theta_chain_dpp on its own.  theta0 [W, 4] (one per 16-lane row), phi [W, 64] (one per lane)

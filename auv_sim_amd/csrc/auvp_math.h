@@ -127,13 +127,21 @@ AUVP_HD double auvp_sqrt_plain(double x) {
 #undef AUVP_ATAN_K
 
 // hypot(x, y) for finite, unexceptional magnitudes (|x|,|y| in ~[1e-140, 1e140]): Borges' fused
-// formulation -- sqrt of the fma'd sum of squares plus one exact-residual correction.
+// formulation -- sqrt of the fma'd sum of squares plus one exact-residual correction.  Correctly rounded there (against
+// arbitrary precision: tests/test_portable_math.py), the same double on host and device (tests/test_gpu_math_edges.py); the
+// callers take hypot(gx - lx, gy - ly) of positions in metres.  BELOW that domain nothing is promised: the squares and the
+// residuals run into the subnormals and lose bits without any signal.  The host build stays exact down to a larger operand of
+// 2^-508 (1.2e-153), is off by an ulp at 2^-512, hypot(1e-160, 0) is off by 5.6e-6 of itself and hypot(1e-162, 1e-162)
+// returns 1e-162.  The device's auvp_sqrt_plain -- which leaves out the input scaling, so that here it gets squares down to
+// 2^-930, far below its own documented 2^-500 -- has been compared with the host's only on the domain.
 AUVP_HD double auvp_hypot(double x, double y) {
   double ax = auvp_fabs(x), ay = auvp_fabs(y);
   if (ax < ay) { double t = ax; ax = ay; ay = t; }
   if (ax == 0.0) return ax;  // (both zero: nothing to divide by; a zero smaller operand falls out of the formula: h = ax, r = 0)
   double h = auvp_sqrt_plain(auvp_fma(ax, ax, ay * ay));
-  if (h == 0.0) return ax;   // (ax^2 underflowed, |ax| < ~2^-511: the correction below would be 0 / 0)
+  // (FULL underflow only -- the sum of squares rounded to 0, |ax| < ~2^-537: the correction below would be 0 / 0.  A sum that is
+  // merely subnormal passes, with the errors described above)
+  if (h == 0.0) return ax;
   double h2 = h * h;
   double ax2 = ax * ax;
   double r = auvp_fma(-ay, ay, h2 - ax2) + auvp_fma(h, h, -h2) - auvp_fma(ax, ax, -ax2);

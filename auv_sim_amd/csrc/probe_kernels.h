@@ -5,6 +5,8 @@
 #ifndef AUVP_PROBE_KERNELS_H
 #define AUVP_PROBE_KERNELS_H
 #include "auvp_exp.h"
+#include "auvp_math_late.h"
+#include "replan_measure.h"
 
 namespace auvp {
 
@@ -114,9 +116,16 @@ __global__ void sincos_probe_kernel(int n, const double* __restrict__ x, double*
 }
 
 // one portable function per op (auvp_math_dev): 0 sin / cos, 1 atan2(a, b), 2 pow(e, a), 3 auvp_div_plain(a, b),
-// 4 auvp_sqrt_plain(a), 5 hypot(a, b), 6 a / b, 7 sqrt(a)
+// 4 auvp_sqrt_plain(a), 5 hypot(a, b), 6 a / b, 7 sqrt(a) -- and the forms that exist on the device alone, as the hot kernels
+// call them: 8 auvp_sincos_sk(a) (constants through scalar registers), 9 auvp_atan2_late(a, b) (constants through an opaque
+// move), 10 auvp_pow_e_t(a, the table's copy in LDS), 11 replan_measure_kernel's bearing replan_atan2_round(a, b,
+// auvp_atan2_late(a, b)), 12 auvp_atan(a) (atan2 never reaches atan's |x| >= 2^66 branch).  The table is staged as
+// pf_step_kernel stages it, by every workgroup (256 threads) and before the bounds test: all threads reach the barrier.
 __global__ void math_probe_kernel(int op, int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ o0,
                                   double* __restrict__ o1) {
+  __shared__ double etab[AUVP_EXP_TBL_DOUBLES];
+  if (threadIdx.x < AUVP_EXP_TBL_DOUBLES) etab[threadIdx.x] = auvp_exp_table()[threadIdx.x];
+  __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double x = a[i], y = b[i];
@@ -129,7 +138,12 @@ __global__ void math_probe_kernel(int op, int n, const double* __restrict__ a, c
     case 4: r0 = auvp_sqrt_plain(x); break;
     case 5: r0 = auvp_hypot(x, y); break;
     case 6: r0 = x / y; break;
-    default: r0 = auvp_sqrt(x); break;
+    case 7: r0 = auvp_sqrt(x); break;
+    case 8: auvp_sincos_sk(x, &r0, &r1); break;
+    case 9: r0 = auvp_atan2_late(x, y); break;
+    case 10: r0 = auvp_pow_e_t(x, etab); break;
+    case 11: r0 = replan_atan2_round(x, y, auvp_atan2_late(x, y)); break;
+    default: r0 = auvp_atan(x); break;
   }
   o0[i] = r0;
   o1[i] = r1;
@@ -307,7 +321,7 @@ int auvp_sincos_dev(auvp_handle* h, int32_t n, const double* x, double* s, doubl
 }
 
 int auvp_math_dev(auvp_handle* h, int32_t op, int32_t n, const double* a, const double* b, double* out0, double* out1) {
-  if (!h || n < 0 || op < 0 || op > 7 || !a || !b || !out0 || !out1) return AUVP_ERR_ARG;
+  if (!h || n < 0 || op < 0 || op > 12 || !a || !b || !out0 || !out1) return AUVP_ERR_ARG;
   if (n == 0) return AUVP_OK;
   HIPCHK(h, hipSetDevice(h->device));
   int rc;

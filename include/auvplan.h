@@ -684,7 +684,10 @@ int auvp_sincos_dev(auvp_handle* h, int32_t n, const double* x, double* s, doubl
  * (bit-exactness probe: the tests compare with the host build of the same header and with the IEEE operation).  op: 0 sin -> out0,
  * cos -> out1 of a (math.sin / math.cos, path_planning/rrt_dubins.py:275-276); 1 atan2(a, b) (gym_rrt/envs/rrt_dubins.py:387);
  * 2 math.e ** a (particleFilter.py:103-116); 3 the steer's short division a / b and 4 its square root (rrt_dubins.py:268-281;
- * operands of unexceptional magnitude: auvp_div_plain / auvp_sqrt_plain); 5 hypot(a, b); 6 a / b and 7 sqrt(a) as compiled. */
+ * operands of unexceptional magnitude: auvp_div_plain / auvp_sqrt_plain); 5 hypot(a, b); 6 a / b and 7 sqrt(a) as compiled.
+ * The forms only device code has, as the kernels call them: 8 sin / cos with the constants in scalar registers (auvp_sincos_sk);
+ * 9 atan2(a, b) with late constants (auvp_atan2_late); 10 math.e ** a reading the table's copy in LDS (auvp_pow_e_t); 11 the
+ * bearing of auvp_replan_measure without the heading, replan_atan2_round(a, b, auvp_atan2_late(a, b)); 12 atan(a). */
 int auvp_math_dev(auvp_handle* h, int32_t op, int32_t n, const double* a, const double* b, double* out0, double* out1);
 /* the four-episode RRT kernels' ordered theta sum (rows_theta_chain_dpp, auv_sim_amd/csrc/rrt_rows_kernel.h) on its own, n_waves
  * wavefronts of four 16-lane rows: theta0 [n_waves * 4] one start angle per row, phi [n_waves * 64] one addend per lane; out

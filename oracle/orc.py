@@ -66,6 +66,8 @@ def lib(kind="libm"):
         L.orc_sin.argtypes = [C.c_double]
         L.orc_cos.restype = C.c_double
         L.orc_cos.argtypes = [C.c_double]
+        L.orc_atan.restype = C.c_double
+        L.orc_atan.argtypes = [C.c_double]
         for fn in (L.orc_atan2, L.orc_hypot):
             fn.restype = C.c_double
             fn.argtypes = [C.c_double, C.c_double]

@@ -166,6 +166,7 @@ const char* orc_math_name(void);
 double orc_sin(double x);
 double orc_cos(double x);
 double orc_atan2(double y, double x);
+double orc_atan(double x);
 double orc_hypot(double x, double y);
 
 void orc_rng_kat(uint64_t seed, int n, double* out_random, uint32_t* out_bits32, int nchoice,

@@ -24,6 +24,7 @@
 #define ORC_POW2(x) ((x) * (x))
 #define ORC_SQRT(x) auvp_sqrt(x)
 #define ORC_ATAN2(y, x) auvp_atan2(y, x)
+#define ORC_ATAN(x) auvp_atan(x)
 #define ORC_HYPOT(x, y) auvp_hypot(x, y)
 #define ORC_POW_E(z) auvp_pow_e(z)
 #define ORC_MATH_NAME "portable"
@@ -33,6 +34,7 @@
 #define ORC_POW2(x) pow((x), 2.0)
 #define ORC_SQRT(x) sqrt(x)
 #define ORC_ATAN2(y, x) atan2(y, x)
+#define ORC_ATAN(x) atan(x)
 #define ORC_HYPOT(x, y) orc_cpython_hypot(x, y)
 #define ORC_POW_E(z) pow(2.718281828459045, (z)) /* math.e ** z */
 #define ORC_MATH_NAME "libm"
