@@ -171,6 +171,8 @@ def load():
     L.auvp_math_dev.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
     if hasattr(L, "auvp_theta_chain_dev"):  # (as above: an earlier build loaded for a comparison has no such probe)
         L.auvp_theta_chain_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    if hasattr(L, "auvp_row_ends_dev"):  # (likewise)
+        L.auvp_row_ends_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     L.auvp_nn_closest_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _ip, _ip]
     L.auvp_random_stream_dev.argtypes = [vp, C.c_uint64, C.c_int32, _dp]
     L.auvp_rrt_phase_clocks.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -893,6 +895,18 @@ class Context:
         assert len(theta0) == len(phi)
         out = np.zeros_like(phi)
         self._chk(self.L.auvp_theta_chain_dev(self.h, len(phi), _p(theta0), _p(phi), _p(out)))
+        return out
+
+    def row_ends(self, n, on, start, incs):
+        """auvp_row_ends_dev: the end of a steer pass of the four-episode RRT kernels on its own.  n [W, 4] sub-arcs per row (1 .. 15),
+        on [W, 4] (0 / 1), start [W, 4, 5] the rows' x, y, t, length, theta, incs [W, 5, 64] every lane's addends -> [W, 5, 64]: the
+        row's x, y, t, length, theta after the pass, as each lane of the row holds them"""
+        start, incs = _f64(start, (-1, 4, 5)), _f64(incs, (-1, 5, 64))
+        head = np.concatenate([_f64(n, (-1, 4, 1)), _f64(on, (-1, 4, 1)), start], axis=2)
+        assert len(head) == len(incs)
+        head = np.ascontiguousarray(head)
+        out = np.zeros_like(incs)
+        self._chk(self.L.auvp_row_ends_dev(self.h, len(incs), _p(head), _p(incs), _p(out)))
         return out
 
     def random_stream(self, seed, n):

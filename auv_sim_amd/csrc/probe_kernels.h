@@ -159,6 +159,36 @@ __global__ __launch_bounds__(64) void theta_chain_probe_kernel(const double* __r
   out[w * 64 + (size_t)lane] = rows_theta_chain_dpp(t0, p);
 }
 
+// The end of a steer pass of the four-episode RRT kernels on its own: the text rrt_rows_body.h runs -- rows_idle_zero for the lanes
+// past n, rows_theta_chain_dpp, the increments' LDS rows, rows_sums_chain, rows_pass_ends_dpp -- one wavefront of four rows per
+// workgroup.  head [7] per row: n, on, then the start x, y, t, length, theta; incs [5][64] per wavefront: what each lane adds to
+// x, y, t, length, theta when it is below n; out [5][64]: the row's state after the pass as every lane got it.  Entry 15 of an
+// LDS row is set to a NaN here: nobody may add it.
+__global__ __launch_bounds__(64) void row_ends_probe_kernel(const double* __restrict__ head, const double* __restrict__ incs,
+                                                            double* __restrict__ out) {
+  __shared__ __align__(16) double inc_s[RW_ROWS][4 * 18];
+  const int lane = lane_id(), row = lane >> 4, rl = lane & 15;
+  const size_t w = blockIdx.x;
+  const double* hd = head + (w * 4 + (size_t)row) * 7;
+  const bool on = hd[1] != 0.0;
+  const int n = on ? (int)hd[0] : 0;
+  double cx = hd[2], cy = hd[3], ctt = hd[4], clen = hd[5], cth = hd[6];
+  const bool active = rl < n;
+  const double zero = rows_idle_zero(active);
+  const double* in = incs + w * 320 + (size_t)lane;
+  const double dx = active ? in[0] : zero, dy = active ? in[64] : zero, dt = active ? in[128] : zero, mv = active ? in[192] : zero;
+  const double phi = active ? in[256] : zero;
+  double* inc = inc_s[row];
+  const double th = rows_theta_chain_dpp(cth, phi);
+  if (rl < 15) { inc[rl] = dx; inc[18 + rl] = dy; inc[36 + rl] = dt; inc[54 + rl] = mv; }
+  else { inc[15] = inc[33] = inc[51] = inc[69] = __builtin_nan(""); }
+  wave_sync();
+  const double acc = rows_sums_chain(inc, rl, on, rl == 0 ? cx : (rl == 1 ? cy : (rl == 2 ? ctt : clen)));
+  rows_pass_ends_dpp(acc, th, cx, cy, ctt, clen, cth);
+  double* o = out + w * 320 + (size_t)lane;
+  o[0] = cx; o[64] = cy; o[128] = ctt; o[192] = clen; o[256] = cth;
+}
+
 __global__ __launch_bounds__(64) void random_probe_kernel(const uint32_t* __restrict__ mt, int n, double* __restrict__ out) {
   __shared__ uint32_t s[624];
   const int lane = lane_id();
@@ -350,6 +380,24 @@ int auvp_theta_chain_dev(auvp_handle* h, int32_t n_waves, const double* theta0, 
                      h->d_tmp2.as<double>());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(out, h->d_tmp2.p, (size_t)n_waves * 64 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return AUVP_OK;
+}
+
+int auvp_row_ends_dev(auvp_handle* h, int32_t n_waves, const double* head, const double* incs, double* out) {
+  if (!h || n_waves < 0 || !head || !incs || !out) return AUVP_ERR_ARG;
+  if (n_waves == 0) return AUVP_OK;
+  for (size_t i = 0; i < (size_t)n_waves * 4; i++)
+    if (!(head[i * 7] >= 1.0 && head[i * 7] <= (double)RW_C)) return AUVP_ERR_ARG;  // a pass has 1 .. 15 sub-arcs
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = upload(h, h->d_tmp0, head, (size_t)n_waves * 28))) return rc;
+  if ((rc = upload(h, h->d_tmp1, incs, (size_t)n_waves * 320))) return rc;
+  HIPCHK(h, h->d_tmp2.reserve((size_t)n_waves * 320 * sizeof(double)));
+  hipLaunchKernelGGL(row_ends_probe_kernel, dim3(n_waves), dim3(64), 0, h->stream, h->d_tmp0.as<double>(), h->d_tmp1.as<double>(),
+                     h->d_tmp2.as<double>());
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(out, h->d_tmp2.p, (size_t)n_waves * 320 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return AUVP_OK;
 }

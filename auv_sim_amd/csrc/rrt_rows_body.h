@@ -296,7 +296,10 @@
       const int mypos = 2 * rl + cbelow;
       const int used = 2 * n + __popc(tmask);
       const bool taken = (tmask >> rl) & 1u;
-      double radius = 0.0, phi = 0.0, vt = 1.0;
+      // what a lane without an arc adds to the five sums: +0.0 for an untaken sub-arc, -0.0 past n (rows_idle_zero: the chains
+      // run on over the idle lanes and end with the values of sub-arc n - 1)
+      const double zero = rows_idle_zero(active);
+      double radius = 0.0, phi = zero, vt = 1.0;
       if (taken) {
         const double dist = py_uniform(0.0, Q.dist_to_end, ROWS_WIN(mypos));
         const double diff = py_uniform(-Q.diff_max, Q.diff_max, ROWS_WIN(mypos + 1));
@@ -312,12 +315,12 @@
       wave_sync();
 #endif
       // theta += phi, left to right: lane s ends with (((theta0 + phi_0) + phi_1) + ... + phi_s); untaken and idle lanes add
-      // an exact 0.0 (rows_theta_chain_dpp: the phis cross the row's lanes as 64-bit DPP broadcasts, no LDS)
+      // an exact zero (rows_theta_chain_dpp: the phis cross the row's lanes as 64-bit DPP broadcasts, no LDS)
       const double th = rows_theta_chain_dpp(cth, phi);
       const double myth = (rl == 15) ? cth : th;  // lane 15: the pass-entry angle
       double sn, cs;
       auvp_sincos_sk(myth, &sn, &cs);
-      double dx = 0.0, dy = 0.0, mv = 0.0, dt = 0.0;
+      double dx = zero, dy = zero, mv = zero, dt = zero;
       {
         const uint32_t below = tmask & ((1u << rl) - 1u);
         const int prev = below ? (31 - __clz((int)below)) : 15;
@@ -329,23 +332,16 @@
           dt = auvp_div_plain(mv, vt);
         }
       }
-      // x += dx; y += dy; t += dt; length += movement: four serial chains per row, lanes 0..3, 18-double rows in LDS
+      // x += dx; y += dy; t += dt; length += movement: four serial chains per row, lanes 0..3, 18-double rows in LDS (entry 15
+      // of a row only fills the last 16-byte pair: rows_sums_chain never adds it, so nobody sets it)
       if (rl < 15) { inc[rl] = dx; inc[18 + rl] = dy; inc[36 + rl] = dt; inc[54 + rl] = mv; }
-      else { inc[15] = 0.0; inc[33] = 0.0; inc[51] = 0.0; inc[69] = 0.0; }  // entry 15 pads the last 16-byte pair
       wave_sync();
-      if (rl < 4 && on) {
-        // entries past n hold exact zeros, so all 16 steps can run: eight independent 16-byte reads up front, sixteen
-        // chained additions, eight writes -- no loop, no round trip per step
-        double acc = rl == 0 ? cx : (rl == 1 ? cy : (rl == 2 ? ctt : clen));
-        double2* rowp = reinterpret_cast<double2*>(inc + rl * 18);
-        double2 v[8];
-#pragma unroll
-        for (int s2 = 0; s2 < 8; s2++) v[s2] = rowp[s2];
-#pragma unroll
-        for (int s2 = 0; s2 < 8; s2++) { acc = acc + v[s2].x; v[s2].x = acc; acc = acc + v[s2].y; v[s2].y = acc; }
-#pragma unroll
-        for (int s2 = 0; s2 < 8; s2++) rowp[s2] = v[s2];
-      }
+      const double acc = rows_sums_chain(inc, rl, on, rl == 0 ? cx : (rl == 1 ? cy : (rl == 2 ? ctt : clen)));
+      // the row's state after this pass = the prefix values of its last sub-arc = where the five chains ended (idle lanes added
+      // -0.0): lanes 0 .. 3's sums and lane 14's angle, already in registers -- no LDS read, no ds_bpermute
+      // (rows_pass_ends_dpp; rows that are not `on` did not run the four chains and added fifteen times -0.0 to their angle:
+      // what they get is the state they had)
+      rows_pass_ends_dpp(acc, th, cx, cy, ctt, clen, cth);
       wave_sync();
       double mx = 0.0, my = 0.0, mt_ = 0.0, ml = 0.0;
       if (active) { mx = inc[rl]; my = inc[18 + rl]; mt_ = inc[36 + rl]; ml = inc[54 + rl]; }
@@ -366,16 +362,7 @@
         __builtin_nontemporal_store(vb, reinterpret_cast<nt_f64x2*>(rb)); __builtin_nontemporal_store(ml, rb + 2);
       }
       ptx[pass] = mx; pty[pass] = my; ptv[pass] = wr;
-      {
-        // the row's state after this pass = the prefix values of its last sub-arc
-        const int last = n > 0 ? n - 1 : 0;
-        const double th_last = row_read_f64(myth, rowbase + last);
-        if (on) {
-          cnt += napp;
-          cx = inc[last]; cy = inc[18 + last]; ctt = inc[36 + last]; clen = inc[54 + last];
-          cth = th_last;
-        }
-      }
+      if (on) cnt += napp;
       ROWS_CONSUME(on && live, b0 + used);  // (a row that just failed keeps its stream position, like the one-episode kernel)
       first_pass = false;
       wave_sync();

@@ -134,6 +134,59 @@ __device__ __forceinline__ double rows_theta_chain_dpp(double theta0, double phi
   return th;
 }
 
+// What a lane of a steer pass of n sub-arcs adds to the pass's five ordered sums when it has no arc of its own: +0.0 below n (an
+// untaken sub-arc), -0.0 from n on (an idle lane).  x + (-0.0) == x for EVERY x, x + (+0.0) == x for every x but -0.0: with -0.0
+// past n a chain that runs on over the idle lanes ends with the value it had at sub-arc n - 1, bit for bit, the sign of a zero
+// sum included -- which is what lets rows_pass_ends_dpp take the row's end state from the chain ends.  The prefix values below n
+// are what they were with +0.0 there (nothing past n goes into them).
+__device__ __forceinline__ double rows_idle_zero(bool below_n) { return below_n ? 0.0 : -0.0; }
+
+// x += dx; y += dy; t += dt; length += movement of a steer pass: four serial chains per row, on lanes 0 .. 3, over the 18-double
+// rows of `inc` (entry j of row q = what lane j of the episode wrote for sum q; rows_idle_zero past n, so all 15 steps can run).
+// Eight independent 16-byte reads up front, fifteen chained additions, eight writes -- no loop, no round trip per step.  The
+// prefix sums replace the increments in place; entry 15 only fills the last 16-byte pair: it is read and written back as it
+// was, never added, and nobody has to set it.  `acc` comes in as the lane's start value (lane 0: x, 1: y, 2: t, 3: length) and
+// leaves, on lanes 0 .. 3 of the rows that are `on`, as the row's sum after the pass.
+__device__ __forceinline__ double rows_sums_chain(double* inc, int rl, bool on, double acc) {
+  if (rl < 4 && on) {
+    double2* rowp = reinterpret_cast<double2*>(inc + rl * 18);
+    double2 v[8];
+#pragma unroll
+    for (int s2 = 0; s2 < 8; s2++) v[s2] = rowp[s2];
+#pragma unroll
+    for (int s2 = 0; s2 < 8; s2++) {
+      acc = acc + v[s2].x; v[s2].x = acc;
+      if (s2 < 7) { acc = acc + v[s2].y; v[s2].y = acc; }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 8; s2++) rowp[s2] = v[s2];
+  }
+  return acc;
+}
+
+// The row's state after a steer pass, in every lane: x, y, t, length = `acc` of lanes 0 .. 3 (rows_sums_chain), theta = `th` of
+// lane 14 (rows_theta_chain_dpp: the sum of all fifteen phis).  Five 64-bit DPP moves (v_mov_b64 row_newbcast) instead of two
+// 16-byte LDS reads and two ds_bpermute with a wait each: the numbers are in registers already.  A row that is not `on` needs no
+// guard of its own: rows_sums_chain did not run for it, so `acc` of its lanes 0 .. 3 still IS its x, y, t, length, and all of its
+// lanes are idle, so its `th` is theta0 + fifteen times -0.0 = theta0, bit for bit.  The moves run with all 64 lanes enabled
+// (the source lanes with them), whatever mask the call finds, and that mask is restored; the kernels call it from wave-uniform
+// control flow.  Wait states: a DPP read needs 2 after a VALU write of the register (`acc`: the chain's last add; `th`: the
+// theta chain's last fmac) -- the two scalar moves and the s_nop are three.
+__device__ __forceinline__ void rows_pass_ends_dpp(double acc, double th, double& x, double& y, double& t, double& len,
+                                                   double& theta) {
+  unsigned long long exec_in;
+#define AUVP_END_MOV(D, S, J) "v_mov_b64_dpp %[" #D "], %[" #S "] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+  __asm__ volatile(
+      "s_mov_b64 %[sv], exec\n\t"
+      "s_mov_b64 exec, -1\n\t"
+      "s_nop 0\n\t"
+      AUVP_END_MOV(x, acc, 0) AUVP_END_MOV(y, acc, 1) AUVP_END_MOV(t, acc, 2) AUVP_END_MOV(len, acc, 3) AUVP_END_MOV(theta, th, 14)
+      "s_mov_b64 exec, %[sv]"
+      : [x] "=&v"(x), [y] "=&v"(y), [t] "=&v"(t), [len] "=&v"(len), [theta] "=&v"(theta), [sv] "=&s"(exec_in)
+      : [acc] "v"(acc), [th] "v"(th));
+#undef AUVP_END_MOV
+}
+
 // Per-row view of the MT19937 stream (state in the episode's LDS block, refilled in place like WaveRng, 16 words per
 // round and row).  pslot / avail / drawn are row-uniform.
 struct RowRng {

@@ -694,6 +694,12 @@ int auvp_math_dev(auvp_handle* h, int32_t op, int32_t n, const double* a, const 
  * [n_waves * 64], lane rl of a row gets (((theta0 + phi_0) + phi_1) + ... + phi_rl) of its row; fifteen steps, so lane 15 gets lane 14's sum (bit-exactness probe: the sums of
  * theta += phi in path_planning/rrt_dubins.py:268-281, left to right) */
 int auvp_theta_chain_dev(auvp_handle* h, int32_t n_waves, const double* theta0, const double* phi, double* out);
+/* the end of a steer pass of the four-episode RRT kernels on its own (rows_idle_zero, rows_sums_chain, rows_pass_ends_dpp,
+ * auv_sim_amd/csrc/rrt_rows_kernel.h), n_waves wavefronts of four 16-lane rows: head [n_waves * 4][7] per row n (1 .. 15 sub-arcs),
+ * on (0 / 1), the start x, y, t, length, theta; incs [n_waves][5][64] what each lane adds to x, y, t, length, theta (lanes from n on
+ * add the kernels' idle value instead); out [n_waves][5][64] the row's x, y, t, length, theta after the pass as every lane of the
+ * row holds them: the left-to-right sums over the first n lanes, or the start values for a row that is not on (bit-exactness probe) */
+int auvp_row_ends_dev(auvp_handle* h, int32_t n_waves, const double* head, const double* incs, double* out);
 /* CPython random() stream of `seed` generated by the wave-level device MT19937 */
 int auvp_random_stream_dev(auvp_handle* h, uint64_t seed, int32_t n, double* out);
 

@@ -18,6 +18,10 @@ Classes (profiles/rows_trip_lgkm.md):
   5  a steer pass's theta chain, from its call to the chain's result: a REGION (the 15 dependent DPP fmacs included)
   6  a steer pass's four chains, from the increments' LDS write to the prefix values read back: a REGION
   7  the stream_ensure calls of a trip (votes and slow path): a REGION
+  8  the selection tail, from the selection loop's exit to the member index `ri` the parent-id request is made with: a REGION
+     (the two draws after the winner's, the winner's count; nothing else in the wave can run beside it)
+  9  a steer pass's tail, from the lanes' own prefix reads to the end of the pass: a REGION (the point stores' issue, the row's
+     end state -- profiles/rows_trip_lds.md)
 A pure wait is `stamp; empty asm that reads the value; stamp`: the compiler puts the value's s_waitcnt between the stamps (check
 the listing: with a read-write operand it copies the registers BEFORE the first stamp and the wait goes with the copies; the
 scheduling barriers round the first stamp keep it in front).  A stamp is itself a scalar-memory read that returns through
@@ -84,6 +88,15 @@ for a in ("        if (!stream_ensure<MIRROR>(rng, search, 16u, rl) && search)",
 after("{ status = AUVP_ST_STREAM; live = false; iters_run = it; search = false; }", OUT % 7)
 after("&& on0) { status = AUVP_ST_STREAM; live = false; iters_run = it; }", OUT % 7)
 after("&& on) { status = AUVP_ST_STREAM; live = false; iters_run = it; }", OUT % 7)
+# 8: the selection tail
+before("      // the two draws after the winner's\n#if AUVP_ROWS_BODY_STREAM", IN % 8)
+after("        const int ri = (int)py_uniform(0.0, (double)cnt, u1);",
+      '\n#ifdef AUVP_ROWS_WAIT_STAMPS\n        if (AUVP_ROWS_WAIT_STAMPS == 8) { asm volatile("" : : "v"(ri)); ROWS_WS_OUT(8); }\n#endif\n')
+# 9: a pass's tail
+before("      if (active) { mx = inc[rl]; my = inc[18 + rl]; mt_ = inc[36 + rl]; ml = inc[54 + rl]; }", IN % 9)
+before("      first_pass = false;\n      wave_sync();",
+       '\n#ifdef AUVP_ROWS_WAIT_STAMPS\n      if (AUVP_ROWS_WAIT_STAMPS == 9) { asm volatile("" : : "v"(cx), "v"(cy), "v"(cth), "v"(ctt), "v"(clen)); '
+       'ROWS_WS_OUT(9); }\n#endif\n')
 # the total, per wave (every row of the wave reports it)
 after("      s.rng_after = after; s.leaf_elems = 0; s.n_draw32 = drawn; s.nn_scanned = 0ull;",
       "\n#ifdef AUVP_ROWS_WAIT_STAMPS\n      s.nn_scanned = ws_acc;\n#endif")

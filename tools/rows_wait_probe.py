@@ -3,6 +3,7 @@
 and built with -DAUVP_ROWS_WAIT_STAMPS=<class> (see there), loaded through AUVPLAN_LIBRARY: every episode's summary then carries
 its wave's stamped shader-clock total in nn_scanned (unused in time-bin mode).  The headline batch, twice (the first batch with a
 parameter block sizes the stream); one JSON line: cycles per wave and trip for the class, beside the stamped kernel's time.
+Classes 1 .. 9 (the patch tool lists them; 8 = the selection tail, 9 = a steer pass's tail: profiles/rows_trip_lds.md).
 usage: AUVPLAN_LIBRARY=... tools/rows_wait_probe.py <class> [episodes] [iterations]"""
 import json
 import os
