@@ -4,40 +4,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._cabi import ASTAR_SUMMARY_DTYPE, AstarParams  # noqa: F401
 
-_dp, _ip = _lib._dp, _lib._ip
 VARIANTS = {"astar": 0, "astar_real": 1, "astar_fixLen": 2, "astar_fixLenSOG": 3}
 
 
-class AstarParams(C.Structure):
-    _fields_ = [("variant", C.c_int32), ("cap_nodes", C.c_int32), ("box", C.c_double * 4), ("velocity", C.c_double),
-                ("w", C.c_double * 4)]
-
-
-ASTAR_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("status", "found", "n_nodes", "n_expansions", "n_children", "path_len",
-                                                     "smooth_len", "n_hab_left", "visited_count", "leaf")] +
-                               [("open_scanned", "<u8")])
-_bound = False
-
-
 def _bind():
-    global _bound
-    L = _lib.load()
-    if _bound:
-        return L
-    vp = C.c_void_p
-    L.auvp_astar_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, C.POINTER(AstarParams), C.c_int32]
-    L.auvp_astar_summaries.argtypes = [vp, C.c_void_p]
-    L.auvp_astar_paths.argtypes = [vp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp]
-    L.auvp_astar_exp_log.argtypes = [vp, C.c_int32, _dp]
-    L.auvp_astar_hab_left.argtypes = [vp, C.c_int32, _ip]
-    L.auvp_astar_set_visited.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
-    L.auvp_astar_get_visited.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint8)]
-    if hasattr(L, "auvp_astar_batch_sets"):  # (an earlier build loaded through AUVPLAN_LIBRARY for a comparison has neither)
-        L.auvp_astar_batch_sets.argtypes = [vp, C.c_int32, _dp, _dp, C.POINTER(AstarParams), C.c_int32, _ip]
-        L.auvp_astar_sets_topn.argtypes = [vp, _dp]
-    _bound = True
-    return L
+    return _lib.load()
 
 
 def sets_topn(ctx):
@@ -53,13 +26,13 @@ def _launch(L, ctx, E, starts, g, lim, p, flags, set_of):
     if set_of is None:
         return ctx._chk(L.auvp_astar_batch(ctx.h, E, _lib._p(starts), _lib._p(g) if g is not None else None,
                                            _lib._p(lim) if lim is not None else None, C.byref(p), flags))
-    so = np.ascontiguousarray(np.asarray(set_of, dtype=np.int32).reshape(-1))
+    so = _lib._arr(set_of, np.int32, (-1,))
     if len(so) != E:
         raise ValueError("set_of has %d entries, expected %d" % (len(so), E))
     if g is not None:
         raise ValueError("set_of is astar_fixLenSOG's: no goals")
     return ctx._chk(L.auvp_astar_batch_sets(ctx.h, E, _lib._p(starts), _lib._p(lim) if lim is not None else None, C.byref(p), flags,
-                                            _lib._p(so, _ip)))
+                                            _lib._p(so)))
 
 
 def run_batch_arrays(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), velocity=1.0, weights=(0, 0, 0, 0),
@@ -80,13 +53,13 @@ def run_batch_arrays(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0
     _launch(L, ctx, E, starts, g, lim, p, 0, set_of)
     batch_ms = ctx.last_kernel_ms()
     summ = np.zeros(E, dtype=ASTAR_SUMMARY_DTYPE)
-    ctx._chk(L.auvp_astar_summaries(ctx.h, summ.ctypes.data_as(C.c_void_p)))
+    ctx._chk(L.auvp_astar_summaries(ctx.h, _lib._p(summ)))
     lens = np.where(summ["found"] != 0, summ["path_len"], 0).astype(np.int64)
     off = np.zeros(E + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     n = max(int(off[-1]), 1)
     path, cost, npath, smooth = np.zeros((n, 3)), np.zeros(n), np.zeros((n, 8)), np.zeros((n, 3))
-    ctx._chk(L.auvp_astar_paths(ctx.h, off.ctypes.data_as(C.POINTER(C.c_int64)), _lib._p(path), _lib._p(cost), _lib._p(npath),
+    ctx._chk(L.auvp_astar_paths(ctx.h, _lib._p(off), _lib._p(path), _lib._p(cost), _lib._p(npath),
                                 _lib._p(smooth)))
     return dict(summ=summ, off=off, path=path, cost_list=cost, node_path=npath, smooth_path=smooth, batch_ms=batch_ms)
 
@@ -109,20 +82,20 @@ def run_batch(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), v
     lim = _lib._f64(limits).reshape(E) if limits is not None else None
     flags = 1 if exp_log else 0
     if visited is not None:  # [E, vx, 600] uint8: the solver's visited_nodes carried over from earlier calls
-        vis = np.ascontiguousarray(visited, dtype=np.uint8)
-        ctx._chk(L.auvp_astar_set_visited(ctx.h, E, p.variant, vis.ctypes.data_as(C.POINTER(C.c_uint8))))
+        vis = _lib._arr(visited, np.uint8)
+        ctx._chk(L.auvp_astar_set_visited(ctx.h, E, p.variant, _lib._p(vis)))
         flags |= 8
     _launch(L, ctx, E, starts, g, lim, p, flags, set_of)
     summ = np.zeros(E, dtype=ASTAR_SUMMARY_DTYPE)
-    ctx._chk(L.auvp_astar_summaries(ctx.h, summ.ctypes.data_as(C.c_void_p)))
+    ctx._chk(L.auvp_astar_summaries(ctx.h, _lib._p(summ)))
     lens = np.where(summ["found"] != 0, summ["path_len"], 0).astype(np.int64)
     off = np.zeros(E + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     n = max(int(off[-1]), 1)
     path, cost, npath, smooth = np.zeros((n, 3)), np.zeros(n), np.zeros((n, 8)), np.zeros((n, 3))
-    ctx._chk(L.auvp_astar_paths(ctx.h, off.ctypes.data_as(C.POINTER(C.c_int64)), _lib._p(path), _lib._p(cost), _lib._p(npath),
+    ctx._chk(L.auvp_astar_paths(ctx.h, _lib._p(off), _lib._p(path), _lib._p(cost), _lib._p(npath),
                                 _lib._p(smooth)))
-    ctx._chk(L.auvp_astar_summaries(ctx.h, summ.ctypes.data_as(C.c_void_p)))  # smooth_len is filled by the path pass
+    ctx._chk(L.auvp_astar_summaries(ctx.h, _lib._p(summ)))  # smooth_len is filled by the path pass
     H = ctx.world_sizes.get("H", 0)
     out = []
     for e in range(E):
@@ -134,11 +107,11 @@ def run_batch(ctx, variant, starts, goals=None, limits=None, box=(0, 0, 0, 0), v
              "node_path": npath[a:b].copy(), "smooth_path": smooth[a:a + int(s["smooth_len"])].copy()}
         hl = np.zeros(max(H, 1), np.int32)
         if H:
-            ctx._chk(L.auvp_astar_hab_left(ctx.h, e, _lib._p(hl, _ip)))
+            ctx._chk(L.auvp_astar_hab_left(ctx.h, e, _lib._p(hl)))
         r["hab_left"] = hl[:int(s["n_hab_left"])]
         if p.variant >= 2 and (visited is not None or return_visited):
             vb = np.zeros((550 if p.variant == 2 else 600, 600), dtype=np.uint8)
-            ctx._chk(L.auvp_astar_get_visited(ctx.h, e, vb.ctypes.data_as(C.POINTER(C.c_uint8))))
+            ctx._chk(L.auvp_astar_get_visited(ctx.h, e, _lib._p(vb)))
             r["visited"] = vb
         if exp_log:
             ex = np.zeros((max(int(s["n_expansions"]), 1), 8))

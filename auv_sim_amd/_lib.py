@@ -8,12 +8,19 @@ import os
 
 import numpy as np
 
+# the structs, constants and prototypes of the C-ABI live in _cabi; the names below stay importable from here
+from ._cabi import (FLAG_ITER_LOG, FLAG_LEAF_LOG, FLAG_PHASE_CLOCKS, KFLAG_NN_EXACT, KFLAG_TIGHT_CULL, MODES,  # noqa: F401
+                    NO_QUALIFYING_LEAF, OK, OPTION_NAMES, EPISODE_DTYPE, GROUP_BEST_DTYPE, REPLAN_RECORD_DTYPE, SUMMARY_DTYPE,
+                    RRTGroupBest, RRTParams, RRTSummary, _PrrtLaunchChoice, _PrrtLaunchQuery, _RrtLaunchChoice, _RrtLaunchQuery,
+                    _SfLaunchChoice, _SfLaunchQuery, bind)
+from ._cabi import bp as _bp, dp as _dp, ip as _ip  # noqa: F401
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AUVPLAN_LIBRARY") or os.path.join(HERE, "libauvplan.so")  # override: kernel experiments
 
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int32)
-_bp = C.POINTER(C.c_int8)
+# numpy element type -> pointer type (what _p picks for an array)
+_PTR = {np.dtype(t): C.POINTER(c) for t, c in (("f8", C.c_double), ("i4", C.c_int32), ("i8", C.c_int64), ("u8", C.c_uint64),
+                                               ("u4", C.c_uint32), ("u1", C.c_uint8), ("i1", C.c_int8))}
 
 
 class AuvpError(RuntimeError):
@@ -21,51 +28,6 @@ class AuvpError(RuntimeError):
         super().__init__("auvplan error %d: %s" % (code, msg))
         self.code = code
 
-
-class RRTParams(C.Structure):
-    _fields_ = [("dist_to_end", C.c_double), ("diff_max", C.c_double), ("freq", C.c_double),
-                ("min_dist", C.c_double), ("bin_interval", C.c_double), ("v", C.c_double),
-                ("max_traj_time", C.c_double), ("max_plan_time", C.c_double), ("w", C.c_double * 3),
-                ("mode", C.c_int32), ("max_iter", C.c_int32), ("points_per_iter", C.c_double)]
-
-
-class RRTSummary(C.Structure):
-    _fields_ = [("status", C.c_int32), ("n_nodes", C.c_int32), ("n_points", C.c_int32),
-                ("n_leaves", C.c_int32), ("best_leaf", C.c_int32), ("best_path_len", C.c_int32),
-                ("iters_run", C.c_int32), ("n_candidates", C.c_int32), ("best_cost", C.c_double * 4),
-                ("best_length", C.c_double), ("rng_after", C.c_double), ("leaf_elems", C.c_int64), ("n_draw32", C.c_uint64),
-                ("nn_scanned", C.c_uint64)]
-
-
-SUMMARY_DTYPE = np.dtype([("status", "<i4"), ("n_nodes", "<i4"), ("n_points", "<i4"), ("n_leaves", "<i4"),
-                          ("best_leaf", "<i4"), ("best_path_len", "<i4"), ("iters_run", "<i4"), ("n_candidates", "<i4"),
-                          ("best_cost", "<f8", (4,)), ("best_length", "<f8"), ("rng_after", "<f8"), ("leaf_elems", "<i8"), ("n_draw32", "<u8"),
-                          ("nn_scanned", "<u8")])
-assert SUMMARY_DTYPE.itemsize == C.sizeof(RRTSummary)
-
-
-
-class RRTGroupBest(C.Structure):
-    """struct auvp_rrt_group_best (include/auvplan.h): the winner of one group of episodes"""
-    _fields_ = [("status", C.c_int32), ("winner", C.c_int32), ("n_with_leaf", C.c_int32), ("path_len", C.c_int32),
-                ("cost", C.c_double * 4), ("length", C.c_double)]
-
-
-GROUP_BEST_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_with_leaf", "<i4"), ("path_len", "<i4"),
-                             ("cost", "<f8", (4,)), ("length", "<f8")])
-assert GROUP_BEST_DTYPE.itemsize == C.sizeof(RRTGroupBest)
-
-# auvp_replan_record (include/auvplan.h): one AUV's round of the device commit step
-REPLAN_RECORD_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_committed", "<i4"), ("path_len", "<i4"),
-                                ("cost", "<f8", (4,)), ("last", "<f8", (7,)), ("keep", "<u8"), ("claimed", "<u8"), ("conflicts", "<i4"),
-                                ("_reserved", "<i4")])
-assert REPLAN_RECORD_DTYPE.itemsize == 128
-
-MODES = {"timebin": 0, "plantime": 1, "nn": 2}
-# auvp_rrt_episode (include/auvplan.h): one episode's own horizon and habitat list (bit h = habitat h of the world's table)
-EPISODE_DTYPE = np.dtype([("max_traj_time", "<f8"), ("habitat_keep", "<u8")])
-FLAG_ITER_LOG, FLAG_LEAF_LOG, FLAG_PHASE_CLOCKS = 1, 2, 4
-OK, NO_QUALIFYING_LEAF = 0, 1
 
 _lib = None
 
@@ -101,119 +63,23 @@ def load():
         raise ImportError("%s is missing: build the HIP extension first "
                           "(python -c 'import __graft_entry__ as g; g.build()')" % LIB_PATH)
     _share_hip_runtime_with_torch()
-    L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.auvp_version.restype = C.c_char_p
-    L.auvp_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.auvp_destroy.argtypes = [vp]
-    L.auvp_destroy.restype = None
-    L.auvp_last_error.argtypes = [vp]
-    L.auvp_last_error.restype = C.c_char_p
-    L.auvp_world_set.argtypes = [vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp,
-                                 C.c_int32, _dp]
-    L.auvp_rrt_explore_batch.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(RRTParams), C.c_int32]
-    L.auvp_rrt_prepare.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(RRTParams), C.c_int32]
-    L.auvp_rrt_prepare_states.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint32), _ip, C.POINTER(RRTParams), C.c_int32]
-    L.auvp_rrt_prepare_episodes.argtypes = [vp, C.c_int32, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _ip,
-                                            C.POINTER(RRTParams), C.c_void_p, C.c_int32]
-    L.auvp_world_set_habitats.argtypes = [vp, _dp, C.c_int32]
-    L.auvp_rrt_run.argtypes = [vp]
-    L.auvp_rrt_paths_dev.argtypes = [vp, C.POINTER(C.c_int64), C.c_void_p]
-    L.auvp_rrt_summaries.argtypes = [vp, C.c_void_p]
-    L.auvp_rrt_paths.argtypes = [vp, C.POINTER(C.c_int64), _dp]
-    L.auvp_rrt_tree.argtypes = [vp, C.c_int32, _dp, _ip, _ip, _ip, _dp]
-    L.auvp_rrt_iter_log.argtypes = [vp, C.c_int32, _ip, _bp, _ip]
-    L.auvp_rrt_leaf_log.argtypes = [vp, C.c_int32, _dp, _ip]
-    L.auvp_rrt_bin_sizes.argtypes = [vp, C.c_int32, _ip, _ip]
-    L.auvp_rrt_summaries_dev.argtypes = [vp]
-    L.auvp_rrt_summaries_dev.restype = C.c_void_p
-    if hasattr(L, "auvp_rrt_group_best"):  # (as below: an earlier build loaded for a comparison has none of them)
-        L.auvp_rrt_group_best.argtypes = [vp, C.c_int32, _ip, C.c_void_p]
-        L.auvp_rrt_group_best_dev.argtypes = [vp]
-        L.auvp_rrt_group_best_dev.restype = C.c_void_p
-        L.auvp_rrt_group_paths.argtypes = [vp, C.POINTER(C.c_int64), _dp]
-        L.auvp_rrt_group_paths_dev.argtypes = [vp, C.POINTER(C.c_int64), C.c_void_p]
-    if hasattr(L, "auvp_world_set_prob_sets"):  # (likewise: probability sets, a table per episode, re-ranking)
-        L.auvp_world_set_prob_sets.argtypes = [vp, C.c_int32, _dp, C.c_void_p]
-        L.auvp_world_prob_set_stats.argtypes = [vp, _dp, _ip]
-        L.auvp_rrt_set_episode_grids.argtypes = [vp, C.c_int32, _ip]
-        L.auvp_rrt_rerank.argtypes = [vp]
-        L.auvp_sf_prob_dev.argtypes = [vp, C.POINTER(C.c_void_p), _ip, _ip, _ip]
-    if hasattr(L, "auvp_world_set_prob_sets_placed"):  # (likewise: the closed tracking loop)
-        L.auvp_world_set_prob_sets_placed.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-        L.auvp_replan_measure.argtypes = [vp, _ip, C.c_int32, _dp, C.POINTER(C.c_void_p)]
-        L.auvp_replan_meas.argtypes = [vp, _ip, _ip, _dp]
-        L.auvp_world_prob_sets_read.argtypes = [vp, _ip, _dp]
-    if hasattr(L, "auvp_sf_last_kernel"):  # (likewise: the forecast on large grids)
-        L.auvp_sf_last_kernel.argtypes = [vp]
-        L.auvp_sf_last_kernel.restype = C.c_char_p
-    if hasattr(L, "auvp_replan_begin"):  # (likewise: the device commit step of replanning_batch)
-        _u64p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
-        L.auvp_replan_begin.argtypes = [vp, C.c_int32, _dp, _u64p, C.c_int32]
-        L.auvp_replan_commit.argtypes = [vp, C.c_int32, _ip, C.c_double, C.c_void_p]
-        L.auvp_replan_traj.argtypes = [vp, _i64p, _dp]
-        L.auvp_replan_commit_courses.argtypes = [vp, C.c_int32, _i64p, _dp, _dp, _u64p, C.c_double, C.c_void_p, _dp]
-        L.auvp_replan_info.argtypes = [vp, _ip, _ip, _i64p, _i64p, _i64p, _dp]
-    if hasattr(L, "auvp_replan_set_teams"):  # (likewise: teams that share one habitat list)
-        L.auvp_replan_set_teams.argtypes = [vp, C.c_int32, _ip]
-        L.auvp_replan_team_fold.argtypes = [vp, C.c_int32, _ip, C.POINTER(C.c_uint64)]
-    if hasattr(L, "auvp_replan_team_pick"):  # (likewise: the team-aware winner selection)
-        L.auvp_replan_team_pick.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_void_p]
-        L.auvp_replan_team_pick_courses.argtypes = [vp, C.c_int32, _ip, _u64p, C.c_int32, _ip, C.c_int32, _i64p, _dp, _dp, _dp, _dp,
-                                                    _ip, _ip, _dp, C.c_void_p, _u64p]
-    if hasattr(L, "auvp_replan_team_pick_apart"):  # (likewise: the selection that keeps teammates' courses apart)
-        L.auvp_replan_team_pick_apart.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]
-        L.auvp_replan_team_pick_apart_courses.argtypes = [vp, C.c_int32, _ip, _u64p, C.c_int32, _ip, C.c_int32, _i64p, _dp, _dp, _dp, _dp,
-                                                          _ip, _ip, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, _u64p, _ip]
-    L.auvp_check_collision_batch.argtypes = [vp, C.c_int32, _ip, _dp, _bp]
-    L.auvp_cost_paths.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _ip, _dp, _dp, _dp]
-    L.auvp_sincos_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
-    L.auvp_math_dev.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
-    if hasattr(L, "auvp_theta_chain_dev"):  # (as above: an earlier build loaded for a comparison has no such probe)
-        L.auvp_theta_chain_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
-    if hasattr(L, "auvp_row_ends_dev"):  # (likewise)
-        L.auvp_row_ends_dev.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
-    L.auvp_nn_closest_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _ip, _ip]
-    L.auvp_random_stream_dev.argtypes = [vp, C.c_uint64, C.c_int32, _dp]
-    L.auvp_rrt_phase_clocks.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.auvp_last_kernel_ms.argtypes = [vp]
-    L.auvp_last_kernel_ms.restype = C.c_double
-    L.auvp_last_launch.argtypes = [vp, _ip, _ip, _ip]
-    L.auvp_rrt_last_launch_parts.argtypes = [vp, _dp, _dp, _ip]
-    L.auvp_rrt_last_leaf_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.auvp_rrt_last_kernel.argtypes = [vp]
-    L.auvp_rrt_last_kernel.restype = C.c_char_p
-    L.auvp_rrt_last_stream_ms.argtypes = [vp]
-    L.auvp_rrt_last_stream_ms.restype = C.c_double
-    L.auvp_rrt_last_stream_len.argtypes = [vp]
-    L.auvp_rrt_last_stream_len.restype = C.c_int64
-    if hasattr(L, "auvp_rrt_last_stream_mirror"):  # (an earlier build loaded through AUVPLAN_LIBRARY for a comparison has neither)
-        L.auvp_rrt_last_stream_mirror.argtypes = [vp]
-        L.auvp_rrt_rows_stream_shape.argtypes = [C.c_int32] * 6 + [_ip, _ip, _ip]
-    L.auvp_hbm_probe.argtypes = [vp, C.c_uint64, C.c_int32, _dp, _dp]
-    L.auvp_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
-    L.auvp_unset_option.argtypes = [vp, C.c_char_p]
-    L.auvp_get_option.argtypes = [vp, C.c_char_p, _ip, C.POINTER(C.c_int64)]
-    L.auvp_pipeline_fallbacks.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
-    _lib = L
-    return L
+    _lib = bind(C.CDLL(LIB_PATH))
+    return _lib
 
 
-# the options of a handle (auvp_set_option).  AUVP_<NAME> in the environment is read ONCE per handle, by
-# auvp_create.
-OPTION_NAMES = ("ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
-                "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
-                "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES",
-                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR", "PRRT_ROWS_GRID", "SF_WIDE_MIN", "SF_WIDE_BLOCK")
-
-
-def _f64(a, shape=None):
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+def _arr(a, dtype, shape=None):
+    """a as a C-contiguous array of dtype (no copy where it already is one), reshaped if a shape is given"""
+    a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
     return a.reshape(shape) if shape is not None else a
 
 
-def _p(a, t=_dp):
-    return a.ctypes.data_as(t)
+def _f64(a, shape=None):
+    return _arr(a, np.float64, shape)
+
+
+def _p(a, t=None):
+    """pointer to a's data: of type t, else of a's own element type (an array of records: a void pointer)"""
+    return a.ctypes.data_as(t or _PTR.get(a.dtype, C.c_void_p))
 
 
 def episode_limits(n_episodes, max_traj_time, habitat_keep, n_habitats, mode="timebin", iter_log=False, phase_clocks=False):
@@ -264,34 +130,8 @@ def rows_stream_shape(K, n_habitats, n_poly, n_bins, waves_wanted=12, force=-1):
     return w.value, bool(m.value), l.value
 
 
-class _RrtLaunchQuery(C.Structure):
-    _fields_ = [("n_episodes", C.c_int32), ("n_cu", C.c_int32), ("mode", C.c_int32), ("max_iter", C.c_int32),
-                ("n_time_bins", C.c_int32), ("flags", C.c_int32), ("freq", C.c_double), ("dist_to_end", C.c_double),
-                ("max_pts", C.c_int32), ("n_obstacles", C.c_int32), ("n_habitats", C.c_int32), ("n_poly", C.c_int32),
-                ("n_bins", C.c_int32), ("obst_area", C.c_double), ("per_episode_limits", C.c_int32), ("one_wave_only", C.c_int32),
-                ("no_stream", C.c_int32), ("seen_E", C.c_int32), ("seen_most", C.c_int64), ("n_options", C.c_int32),
-                ("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
-
-
-class _RrtLaunchChoice(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "J", "quad", "grid", "block", "lds", "lds_max", "kflags", "stream_waves",
-                                         "mirror", "_pad")] + [("stream_len", C.c_int64), ("lds_need", C.c_int64), ("name", C.c_char_p)]
-
-
-class _PrrtLaunchQuery(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_episodes", "n_cu", "n_obstacles", "max_pts", "cap_nodes", "n_buckets", "max_step", "flags")] + \
-               [("freq", C.c_double)] + [(n, C.c_int32) for n in ("step_mode", "waits", "one_wave_only", "rows", "n_options", "_pad")] + \
-               [("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
-
-
-class _PrrtLaunchChoice(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "lat", "rows", "pipe", "draw_wave", "next_lds", "bk_lds", "obst_lds", "eps_wg",
-                                         "grid", "block", "lds", "J")] + [("lds_need", C.c_int64), ("name", C.c_char_p)]
-
-
 RRT_KINDS = ("explore", "explore_lim", "duo", "trio", "rows", "rows_stream")
 PRRT_KINDS = ("one", "pipe", "rows")
-KFLAG_TIGHT_CULL, KFLAG_NN_EXACT = 1024, 2048
 
 
 def _ask_launch(fn, query, choice, options, kinds):
@@ -340,15 +180,6 @@ def prrt_choose_launch(E, n_cu=256, O=0, freq=10.0, max_step=300, n_buckets=0, f
     return _ask_launch("auvp_prrt_choose_launch", q, _PrrtLaunchChoice(), options, PRRT_KINDS)
 
 
-class _SfLaunchQuery(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("rows", "cols", "n_cells", "widest_level", "allow_large", "n_options")] + \
-               [("option_names", C.POINTER(C.c_char_p)), ("option_values", C.POINTER(C.c_int64))]
-
-
-class _SfLaunchChoice(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("status", "kind", "block", "lds")] + [("name", C.c_char_p)]
-
-
 SF_KINDS = ("one-wave", "wide")
 
 
@@ -369,13 +200,11 @@ def forecast_plan(rows, cols, cell_rc):
     earlier in the list, else 1 + the highest level among the earlier neighbours), order [C] (list positions sorted by (level,
     position)), level_off [n_levels + 1], n_levels.  AuvpError (AUVP_ERR_ARG): a cell outside the grid, a cell listed twice,
     an empty list."""
-    L = load()
-    L.auvp_sf_plan.argtypes = [C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _ip]
-    rc = np.ascontiguousarray(np.asarray(cell_rc, dtype=np.int32).reshape(-1, 2))
+    rc = _arr(cell_rc, np.int32, (-1, 2))
     n = len(rc)
     level, order, off = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.int32)
     nl = C.c_int32()
-    code = L.auvp_sf_plan(int(rows), int(cols), _p(rc, _ip), n, _p(level, _ip), _p(order, _ip), _p(off, _ip), C.byref(nl))
+    code = load().auvp_sf_plan(int(rows), int(cols), _p(rc), n, _p(level), _p(order), _p(off), C.byref(nl))
     if code != 0:
         raise AuvpError(code, "auvp_sf_plan: a cell outside the %d x %d grid, a cell listed twice, or an empty list" % (rows, cols))
     return dict(level=level[:n], order=order[:n], level_off=off[:nl.value + 1], n_levels=nl.value)
@@ -503,7 +332,7 @@ class Context:
         """(absmax [G], one_sign [G]) of the handle's probability sets, as the device computed them"""
         n_sets = self.n_prob_sets if n_sets is None else int(n_sets)
         a, s = np.zeros(max(int(n_sets), 1)), np.zeros(max(int(n_sets), 1), np.int32)
-        self._chk(self.L.auvp_world_prob_set_stats(self.h, _p(a), _p(s, _ip)))
+        self._chk(self.L.auvp_world_prob_set_stats(self.h, _p(a), _p(s)))
         return a[:n_sets], s[:n_sets]
 
     def rrt_set_episode_grids(self, set_of):
@@ -512,8 +341,8 @@ class Context:
         if set_of is None:
             self._chk(self.L.auvp_rrt_set_episode_grids(self.h, 0, None))
             return
-        so = np.ascontiguousarray(np.asarray(set_of, dtype=np.int32).reshape(-1))
-        self._chk(self.L.auvp_rrt_set_episode_grids(self.h, len(so), _p(so, _ip)))
+        so = _arr(set_of, np.int32, (-1,))
+        self._chk(self.L.auvp_rrt_set_episode_grids(self.h, len(so), _p(so)))
 
     def rrt_rerank(self, summaries=True):
         """the leaf ranking alone on the last run's trees, under the current assignment (auvp_rrt_rerank)"""
@@ -564,10 +393,10 @@ class Context:
                                                 phase_clocks)
         states = None
         if isinstance(seeds, tuple):  # (mt [E,624] uint32, index [E]) as random.getstate() reports
-            states = np.ascontiguousarray(np.asarray(seeds[0], dtype=np.uint32).reshape(E, 624))
-            sidx = np.ascontiguousarray(np.asarray(seeds[1], dtype=np.int32).reshape(E))
+            states = _arr(seeds[0], np.uint32, (E, 624))
+            sidx = _arr(seeds[1], np.int32, (E,))
         else:
-            seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(E))
+            seeds = _arr(seeds, np.uint64, (E,))
         p = RRTParams()
         p.dist_to_end, p.diff_max, p.freq, p.min_dist = float(dist_to_end), float(diff_max), float(freq), float(min_dist)
         p.bin_interval, p.v, p.max_traj_time = float(bin_interval), float(v), float(max_traj_time)
@@ -578,22 +407,19 @@ class Context:
         flags = (FLAG_ITER_LOG if iter_log else 0) | (FLAG_LEAF_LOG if leaf_log else 0) | (FLAG_PHASE_CLOCKS if phase_clocks else 0)
         if lim is not None:
             self._chk(self.L.auvp_rrt_prepare_episodes(
-                self.h, E, _p(init), None if states is not None else seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                states.ctypes.data_as(C.POINTER(C.c_uint32)) if states is not None else None,
-                _p(sidx, _ip) if states is not None else None, C.byref(p), lim.ctypes.data_as(C.c_void_p), flags))
+                self.h, E, _p(init), None if states is not None else _p(seeds), _p(states) if states is not None else None,
+                _p(sidx) if states is not None else None, C.byref(p), _p(lim), flags))
         elif states is not None:
-            self._chk(self.L.auvp_rrt_prepare_states(self.h, E, _p(init), states.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                     _p(sidx, _ip), C.byref(p), flags))
+            self._chk(self.L.auvp_rrt_prepare_states(self.h, E, _p(init), _p(states), _p(sidx), C.byref(p), flags))
         else:
-            self._chk(self.L.auvp_rrt_prepare(self.h, E, _p(init), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                              C.byref(p), flags))
+            self._chk(self.L.auvp_rrt_prepare(self.h, E, _p(init), _p(seeds), C.byref(p), flags))
         self.n_episodes, self.max_iter = E, int(n_iter)
         if shark_set is not None:
             self.rrt_set_episode_grids(shark_set)
 
     def summaries(self):
         out = np.zeros(self.n_episodes, dtype=SUMMARY_DTYPE)
-        self._chk(self.L.auvp_rrt_summaries(self.h, out.ctypes.data_as(C.c_void_p)))
+        self._chk(self.L.auvp_rrt_summaries(self.h, _p(out)))
         return out
 
     def paths(self, summaries):
@@ -602,14 +428,14 @@ class Context:
         off = np.zeros(self.n_episodes + 1, dtype=np.int64)
         np.cumsum(lens, out=off[1:])
         out = np.zeros((max(int(off[-1]), 1), 7))
-        self._chk(self.L.auvp_rrt_paths(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), _p(out)))
+        self._chk(self.L.auvp_rrt_paths(self.h, _p(off), _p(out)))
         return [out[off[e]:off[e + 1]] for e in range(self.n_episodes)]
 
     def paths_dev(self, offsets, out_dev_ptr):
         """final courses written to a caller-owned device buffer [offsets[E],7] f64 (e.g. a torch tensor's
         data_ptr()) -- stays in HBM for the multi-GPU gather"""
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        self._chk(self.L.auvp_rrt_paths_dev(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(out_dev_ptr)))
+        off = _arr(offsets, np.int64)
+        self._chk(self.L.auvp_rrt_paths_dev(self.h, _p(off), C.c_void_p(out_dev_ptr)))
 
     # ---- best-of-K: the winner of every group of episodes, chosen on the device ----
     def rrt_group_best(self, group_off):
@@ -617,10 +443,10 @@ class Context:
         group_off[g+1]-1, the groups partition the batch.  Returns [G] GROUP_BEST_DTYPE records: status (0, NO_QUALIFYING_LEAF,
         or the status < 0 of the lowest-indexed failed member), winner (episode index or -1), n_with_leaf, and the winner's
         path_len, cost [4], length."""
-        off = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+        off = _arr(group_off, np.int32, (-1,))
         G = len(off) - 1
         out = np.zeros(max(G, 1), dtype=GROUP_BEST_DTYPE)
-        self._chk(self.L.auvp_rrt_group_best(self.h, G, _p(off, _ip), out.ctypes.data_as(C.c_void_p)))
+        self._chk(self.L.auvp_rrt_group_best(self.h, G, _p(off), _p(out)))
         return out[:G]
 
     def group_best_dev(self):
@@ -640,13 +466,13 @@ class Context:
         rows are copied to the host."""
         off = self.group_offsets(best)
         out = np.zeros((max(int(off[-1]), 1), 7))
-        self._chk(self.L.auvp_rrt_group_paths(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), _p(out)))
+        self._chk(self.L.auvp_rrt_group_paths(self.h, _p(off), _p(out)))
         return [out[off[g]:off[g + 1]] for g in range(len(best))]
 
     def group_paths_dev(self, offsets, out_dev_ptr):
         """the winners' courses written to a caller-owned device buffer [offsets[G],7] f64"""
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        self._chk(self.L.auvp_rrt_group_paths_dev(self.h, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(out_dev_ptr)))
+        off = _arr(offsets, np.int64)
+        self._chk(self.L.auvp_rrt_group_paths_dev(self.h, _p(off), C.c_void_p(out_dev_ptr)))
 
     # ---- replanning a fleet with the commit step on the device (include/auvplan.h: auvp_replan_*) ----
     def replan_begin(self, start7, keep0):
@@ -654,10 +480,10 @@ class Context:
         habitat bit mask or [N]; an empty trajectory log"""
         self._not_in_session("replan_begin")
         s = _f64(start7, (-1, 7))
-        k = np.ascontiguousarray(np.asarray(keep0, dtype=np.uint64).reshape(-1))
+        k = _arr(keep0, np.uint64, (-1,))
         if len(k) not in (1, len(s)):
             raise ValueError("keep0 must be one mask or one per AUV")
-        self._chk(self.L.auvp_replan_begin(self.h, len(s), _p(s), k.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if len(k) == 1 and len(s) != 1 else 0))
+        self._chk(self.L.auvp_replan_begin(self.h, len(s), _p(s), _p(k), 1 if len(k) == 1 and len(s) != 1 else 0))
         self.n_replan_auvs = len(s)
 
     def replan_set_teams(self, team_of):
@@ -667,26 +493,26 @@ class Context:
         if team_of is None:
             self._chk(self.L.auvp_replan_set_teams(self.h, self.n_replan_auvs, None))
             return
-        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
-        self._chk(self.L.auvp_replan_set_teams(self.h, len(t), _p(t, _ip)))
+        t = _arr(team_of, np.int32, (-1,))
+        self._chk(self.L.auvp_replan_set_teams(self.h, len(t), _p(t)))
 
     def replan_team_fold(self, team_of, keep):
         """probe: replan_team_kernel on the caller's labels [n] and keep masks [n], one launch; returns the folded masks [n]
         (uint64).  Needs no world and no fleet, and touches neither."""
-        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
+        t = _arr(team_of, np.int32, (-1,))
         kp = np.array(keep, dtype=np.uint64).reshape(-1)
         if len(kp) != len(t):
             raise ValueError("team_of has %d entries, keep %d" % (len(t), len(kp)))
-        self._chk(self.L.auvp_replan_team_fold(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._chk(self.L.auvp_replan_team_fold(self.h, len(t), _p(t), _p(kp)))
         return kp
 
     def replan_team_pick(self, auv_of, K):
         """the team-aware winner selection in place of rrt_group_best (auvp_replan_team_pick): group g of the batch that just
         ran = episodes g*K .. g*K+K-1 = AUV auv_of[g].  Returns [n_active] GROUP_BEST_DTYPE records: rrt_group_best's for AUVs
         without a teammate, the winner under the teammates' claims and its score for the members of teams."""
-        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        a = _arr(auv_of, np.int32, (-1,))
         out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
-        self._chk(self.L.auvp_replan_team_pick(self.h, len(a), _p(a, _ip), int(K), out.ctypes.data_as(C.c_void_p)))
+        self._chk(self.L.auvp_replan_team_pick(self.h, len(a), _p(a), int(K), _p(out)))
         return out[:len(a)]
 
     def replan_team_pick_apart(self, auv_of, K, use_claims, d, tick, W):
@@ -694,10 +520,10 @@ class Context:
         (auvp_replan_team_pick_apart): d metres, tick seconds, W ticks per course; use_claims: the scores under the teammates'
         claims, as replan_team_pick's.  Returns [n_active] GROUP_BEST_DTYPE records; the conflict counts come back in the
         records of the replan_commit behind it."""
-        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        a = _arr(auv_of, np.int32, (-1,))
         out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
-        self._chk(self.L.auvp_replan_team_pick_apart(self.h, len(a), _p(a, _ip), int(K), 1 if use_claims else 0, float(d), float(tick), int(W),
-                                                     out.ctypes.data_as(C.c_void_p)))
+        self._chk(self.L.auvp_replan_team_pick_apart(self.h, len(a), _p(a), int(K), 1 if use_claims else 0, float(d), float(tick), int(W),
+                                                     _p(out)))
         return out[:len(a)]
 
     def replan_team_pick_apart_courses(self, team_of, keep, auv_of, K, courses_xyt, cost4, leaf_t, length, bin_lo, bin_hi, weights,
@@ -712,9 +538,9 @@ class Context:
         the world's habitat table and time bins.  courses_xyt: n_active * K arrays [L,3] (L == 0: a tree without a leaf), in
         group order; cost4 [E,4], leaf_t [E], length [E], bin_lo / bin_hi [E].  Returns (records [n_active], claimed [n_active]).
         apart: replan_team_pick_apart_courses' arguments."""
-        t = np.ascontiguousarray(np.asarray(team_of, dtype=np.int32).reshape(-1))
+        t = _arr(team_of, np.int32, (-1,))
         kp = np.array(keep, dtype=np.uint64).reshape(-1)
-        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        a = _arr(auv_of, np.int32, (-1,))
         E = len(a) * int(K)
         if len(kp) != len(t) or len(courses_xyt) != E:
             raise ValueError("team_of / keep, or auv_of x K / courses, do not match")
@@ -724,38 +550,31 @@ class Context:
         if len(flat) == 0:
             flat = np.zeros((1, 3))
         c4, lt, ln = _f64(cost4, (E, 4)), _f64(leaf_t, (E,)), _f64(length, (E,))
-        lo = np.ascontiguousarray(np.asarray(bin_lo, dtype=np.int32).reshape(E))
-        hi = np.ascontiguousarray(np.asarray(bin_hi, dtype=np.int32).reshape(E))
+        lo = _arr(bin_lo, np.int32, (E,))
+        hi = _arr(bin_hi, np.int32, (E,))
         w = _f64(weights, (3,))
         out = np.zeros(max(len(a), 1), dtype=GROUP_BEST_DTYPE)
         claimed = np.zeros(max(len(a), 1), dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
+        cand = (len(t), _p(t), _p(kp), len(a), _p(a), int(K), _p(off), _p(flat), _p(c4), _p(lt), _p(ln), _p(lo), _p(hi), _p(w))
         if apart is not None:
             conflicts = np.zeros(max(len(a), 1), dtype=np.int32)
-            self._chk(self.L.auvp_replan_team_pick_apart_courses(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(u64p), len(a), _p(a, _ip), int(K),
-                                                                 off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(c4), _p(lt), _p(ln),
-                                                                 _p(lo, _ip), _p(hi, _ip), _p(w), apart[0], apart[1], apart[2], apart[3],
-                                                                 out.ctypes.data_as(C.c_void_p), claimed.ctypes.data_as(u64p), _p(conflicts, _ip)))
+            self._chk(self.L.auvp_replan_team_pick_apart_courses(self.h, *cand, *apart, _p(out), _p(claimed), _p(conflicts)))
             return out[:len(a)], claimed[:len(a)], conflicts[:len(a)]
-        self._chk(self.L.auvp_replan_team_pick_courses(self.h, len(t), _p(t, _ip), kp.ctypes.data_as(u64p), len(a), _p(a, _ip), int(K),
-                                                       off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(c4), _p(lt), _p(ln),
-                                                       _p(lo, _ip), _p(hi, _ip), _p(w), out.ctypes.data_as(C.c_void_p),
-                                                       claimed.ctypes.data_as(u64p)))
+        self._chk(self.L.auvp_replan_team_pick_courses(self.h, *cand, _p(out), _p(claimed)))
         return out[:len(a)], claimed[:len(a)]
 
     def replan_commit(self, auv_of, round_span, records=True):
         """one round behind rrt_group_best: group g is AUV auv_of[g]; the winners' first buckets go into the log, the states
         are updated in HBM.  Returns [n_active] REPLAN_RECORD_DTYPE records (None with records=False)."""
-        a = np.ascontiguousarray(np.asarray(auv_of, dtype=np.int32).reshape(-1))
+        a = _arr(auv_of, np.int32, (-1,))
         out = np.zeros(max(len(a), 1), dtype=REPLAN_RECORD_DTYPE) if records else None
-        self._chk(self.L.auvp_replan_commit(self.h, len(a), _p(a, _ip), float(round_span),
-                                            out.ctypes.data_as(C.c_void_p) if records else None))
+        self._chk(self.L.auvp_replan_commit(self.h, len(a), _p(a), float(round_span), _p(out) if records else None))
         return out[:len(a)] if records else None
 
     def replan_measure(self, shark_of, n_per_shark, shark_xy):
         """auvp_replan_measure: the fleet's measurements [F, A, 5] of the sharks at shark_xy [F,2] from its committed states,
         left in HBM.  Returns the table's device pointer (valid until the next call or replan_begin)."""
-        so = np.ascontiguousarray(np.asarray(shark_of, dtype=np.int32).reshape(-1))
+        so = _arr(shark_of, np.int32, (-1,))
         if len(so) != self.n_replan_auvs:
             raise ValueError("shark_of has %d entries, the fleet %d AUVs" % (len(so), self.n_replan_auvs))
         A = int(n_per_shark)
@@ -766,7 +585,7 @@ class Context:
             raise ValueError("every shark 0 .. %d must be tracked by exactly %d AUVs" % (F - 1, A))
         xy = _f64(shark_xy, (F, 2))
         ptr = C.c_void_p()
-        self._chk(self.L.auvp_replan_measure(self.h, _p(so, _ip), A, _p(xy), C.byref(ptr)))
+        self._chk(self.L.auvp_replan_measure(self.h, _p(so), A, _p(xy), C.byref(ptr)))
         return ptr.value
 
     def replan_meas(self):
@@ -780,11 +599,10 @@ class Context:
     def replan_traj(self):
         """(row_off [N+1], rows [row_off[N],7]): every AUV's committed trajectory in round order -- the one bulk download"""
         off = np.zeros(self.n_replan_auvs + 1, dtype=np.int64)
-        i64p = C.POINTER(C.c_int64)
-        self._chk(self.L.auvp_replan_traj(self.h, off.ctypes.data_as(i64p), None))
+        self._chk(self.L.auvp_replan_traj(self.h, _p(off), None))
         rows = np.zeros((int(off[-1]), 7))
         if len(rows):
-            self._chk(self.L.auvp_replan_traj(self.h, off.ctypes.data_as(i64p), _p(rows)))
+            self._chk(self.L.auvp_replan_traj(self.h, _p(off), _p(rows)))
         return off, rows
 
     def replan_commit_courses(self, courses, last7, keep, round_span):
@@ -799,9 +617,8 @@ class Context:
         kp = np.array(keep, dtype=np.uint64).reshape(n)
         out = np.zeros(max(n, 1), dtype=REPLAN_RECORD_DTYPE)
         rows = np.zeros((max(len(flat), 1), 7))
-        self._chk(self.L.auvp_replan_commit_courses(self.h, n, off.ctypes.data_as(C.POINTER(C.c_int64)), _p(flat), _p(last),
-                                                    kp.ctypes.data_as(C.POINTER(C.c_uint64)), float(round_span),
-                                                    out.ctypes.data_as(C.c_void_p), _p(rows)))
+        self._chk(self.L.auvp_replan_commit_courses(self.h, n, _p(off), _p(flat), _p(last), _p(kp), float(round_span), _p(out),
+                                                    _p(rows)))
         return out[:n], [rows[off[i]:off[i] + out[i]["n_committed"]] for i in range(n)], last, kp
 
     def replan_info(self):
@@ -820,26 +637,26 @@ class Context:
         pt_off = np.zeros(n, np.int32)
         pt_cnt = np.zeros(n, np.int32)
         points = np.zeros((max(npnt, 1), 7))
-        self._chk(self.L.auvp_rrt_tree(self.h, ep, _p(nodes), _p(parent, _ip), _p(pt_off, _ip), _p(pt_cnt, _ip), _p(points)))
+        self._chk(self.L.auvp_rrt_tree(self.h, ep, _p(nodes), _p(parent), _p(pt_off), _p(pt_cnt), _p(points)))
         return dict(nodes=nodes, parent=parent, pt_off=pt_off, pt_cnt=pt_cnt, points=points[:npnt])
 
     def iter_log(self, ep):
         n = self.max_iter
         a, b, c = np.zeros(n, np.int32), np.zeros(n, np.int8), np.zeros(n, np.int32)
-        self._chk(self.L.auvp_rrt_iter_log(self.h, ep, _p(a, _ip), _p(b, _bp), _p(c, _ip)))
+        self._chk(self.L.auvp_rrt_iter_log(self.h, ep, _p(a), _p(b), _p(c)))
         return dict(it_parent=a, it_accepted=b, it_npath=c)
 
     def leaf_log(self, ep, summary):
         n = int(summary["n_leaves"])
         lc, li = np.zeros((max(n, 1), 6)), np.zeros(max(n, 1), np.int32)
-        self._chk(self.L.auvp_rrt_leaf_log(self.h, ep, _p(lc), _p(li, _ip)))
+        self._chk(self.L.auvp_rrt_leaf_log(self.h, ep, _p(lc), _p(li)))
         return lc[:n], li[:n]
 
     def bin_sizes(self, ep):
         k = C.c_int32()
         self._chk(self.L.auvp_rrt_bin_sizes(self.h, ep, None, C.byref(k)))
         s = np.zeros(max(k.value, 1), np.int32)
-        self._chk(self.L.auvp_rrt_bin_sizes(self.h, ep, _p(s, _ip), C.byref(k)))
+        self._chk(self.L.auvp_rrt_bin_sizes(self.h, ep, _p(s), C.byref(k)))
         return s[:k.value]
 
     # ---- probes ----
@@ -848,7 +665,7 @@ class Context:
         off[1:] = np.cumsum([len(p) for p in paths_xy])
         pts = _f64(np.concatenate([_f64(p, (-1, 2)) for p in paths_xy]) if len(paths_xy) else [], (-1, 2))
         out = np.zeros(len(paths_xy), np.int8)
-        self._chk(self.L.auvp_check_collision_batch(self.h, len(paths_xy), _p(off, _ip), _p(pts), _p(out, _bp)))
+        self._chk(self.L.auvp_check_collision_batch(self.h, len(paths_xy), _p(off), _p(pts), _p(out)))
         return out.astype(bool)
 
     def cost_paths(self, paths_xyt, bin_lo, bin_hi, total, weights):
@@ -856,19 +673,19 @@ class Context:
         off = np.zeros(n + 1, np.int32)
         off[1:] = np.cumsum([len(p) for p in paths_xyt])
         pts = _f64(np.concatenate([_f64(p, (-1, 3)) for p in paths_xyt]), (-1, 3))
-        lo = np.ascontiguousarray(bin_lo, dtype=np.int32)
-        hi = np.ascontiguousarray(bin_hi, dtype=np.int32)
+        lo = _arr(bin_lo, np.int32)
+        hi = _arr(bin_hi, np.int32)
         tt = _f64(total)
         w = _f64(weights, (n, 3))
         out = np.zeros((n, 4))
-        self._chk(self.L.auvp_cost_paths(self.h, n, _p(off, _ip), _p(pts), _p(lo, _ip), _p(hi, _ip), _p(tt), _p(w), _p(out)))
+        self._chk(self.L.auvp_cost_paths(self.h, n, _p(off), _p(pts), _p(lo), _p(hi), _p(tt), _p(w), _p(out)))
         return out
 
     def nn_closest(self, xy, queries, force_exact=False):
         """get_closest_mps (rrt_dubins.py:505-513) of every query point against the node list xy -> (index, slow-path flag)"""
         xy, q = _f64(xy, (-1, 2)), _f64(queries, (-1, 2))
         idx, slow = np.zeros(len(q), np.int32), np.zeros(len(q), np.int32)
-        self._chk(self.L.auvp_nn_closest_batch(self.h, len(xy), _p(xy), len(q), _p(q), 1 if force_exact else 0, _p(idx, _ip), _p(slow, _ip)))
+        self._chk(self.L.auvp_nn_closest_batch(self.h, len(xy), _p(xy), len(q), _p(q), 1 if force_exact else 0, _p(idx), _p(slow)))
         return idx, slow.astype(bool)
 
     def sincos(self, x):
@@ -916,13 +733,11 @@ class Context:
 
     def phase_clocks(self):
         out = np.zeros((self.n_episodes, 5), dtype=np.uint64)
-        self._chk(self.L.auvp_rrt_phase_clocks(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._chk(self.L.auvp_rrt_phase_clocks(self.h, _p(out)))
         return out
 
     def prrt_last_kernel(self):
         """name of the kernel the last Planner_RRT launch ran (prrt_kernel: one episode per wavefront; prrt_rows_kernel: four)"""
-        self.L.auvp_prrt_last_kernel.restype = C.c_char_p
-        self.L.auvp_prrt_last_kernel.argtypes = [C.c_void_p]
         return (self.L.auvp_prrt_last_kernel(self.h) or b"").decode()
 
     def last_kernel_ms(self):

@@ -121,32 +121,13 @@ class RcclGather:
     def library():
         """path of the RCCL image the C-ABI bound (or why none could be)"""
         from . import _lib
-        L = _lib.load()
-        L.auvp_comm_library.restype = C.c_char_p
-        return (L.auvp_comm_library() or b"").decode()
+        return (_lib.load().auvp_comm_library() or b"").decode()
 
     def __init__(self, ctx, rank, world, exchange_id, L=None):
         """`L`: the bound C-ABI (default: libauvplan.so); the CPU tests pass a stand-in with the same entry points"""
         from . import _lib
         self.ctx, self.rank, self.world = ctx, int(rank), int(world)
-        if L is not None:
-            self.L = L
-            self._join(exchange_id)
-            return
-        L = _lib.load()
-        L.auvp_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
-        L.auvp_comm_init.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
-        L.auvp_comm_destroy.argtypes = [C.c_void_p]
-        L.auvp_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.auvp_gather_var.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.auvp_gather_counts.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.auvp_gather_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.auvp_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.auvp_last_gather_ms.argtypes = [C.c_void_p]
-        L.auvp_last_gather_ms.restype = C.c_double
-        L.auvp_gather_blocks_root_async.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.auvp_gather_wait.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        self.L = L
+        self.L = L if L is not None else _lib.load()
         self._join(exchange_id)
 
     def _join(self, exchange_id):

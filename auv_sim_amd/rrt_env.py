@@ -48,16 +48,6 @@ class RRTEnvBatch:
 
         self._auv, self._shark = _many(auv_init_pos), _many(shark_init_pos)
         self._L = _bind()
-        self._L.auvp_prrt_observation.argtypes = [C.c_void_p, C.c_int32, _lib._dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        self._L.auvp_prrt_observation_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._L.auvp_prrt_env_step_dev.argtypes = [C.c_void_p] * 7
-        self._L.auvp_prrt_env_step_ex_dev.argtypes = [C.c_void_p, C.c_int32, C.c_uint64] + [C.c_void_p] * 6
-        self._L.auvp_prrt_env_check.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        self._L.auvp_prrt_policy_random_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-        self._L.auvp_stream_sync.argtypes = [C.c_void_p]
-        self._L.auvp_graph_begin.argtypes = [C.c_void_p]
-        self._L.auvp_graph_end.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        self._L.auvp_graph_launch.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         self._pb = None
         self.state = None
 
@@ -226,8 +216,6 @@ class RRTEnvBatch:
     def timed(self, enqueue):
         """device time in ms (HIP events on the planner's stream) of what `enqueue()` puts on it; waits for it"""
         L = self._L
-        L.auvp_stream_mark.argtypes = [C.c_void_p, C.c_int32]
-        L.auvp_stream_elapsed_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._ctx._chk(L.auvp_stream_mark(self._ctx.h, 0))
         enqueue()
         self._ctx._chk(L.auvp_stream_mark(self._ctx.h, 1))
@@ -346,10 +334,7 @@ class RRTEnv:
         grid = np.zeros((nb, 4))
         has = np.zeros(nb, dtype=np.int64)
         num = np.zeros(nb, dtype=np.int64)
-        L = _bind()
-        L.auvp_prrt_observation.argtypes = [C.c_void_p, C.c_int32, _lib._dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        pb.ctx._chk(L.auvp_prrt_observation(pb.ctx.h, 0, _lib._p(grid), has.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            num.ctypes.data_as(C.POINTER(C.c_int64))))
+        pb.ctx._chk(pb.L.auvp_prrt_observation(pb.ctx.h, 0, _lib._p(grid), _lib._p(has), _lib._p(num)))
         return grid, has, num
 
     def step(self, chosen_grid_cell_idx, step_num):

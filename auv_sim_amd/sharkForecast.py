@@ -27,14 +27,12 @@ HBM (`auvp_sf_prob_dev` -> `auvp_world_set_prob_sets`), and `shark_of=[...]` on 
 ONE grid of its own (the constructor's); the F tables are probability sets beside it, over the same bins and cells.  No CPU
 path: raises without the library / a GPU.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
 
-_dp, _ip = _lib._dp, _lib._ip
 ZERO_TOTAL = 1  # per-filter status: the correction's total is 0 (the reference's ZeroDivisionError)
 MAX_GRID, MAX_GRID_LARGE = 4096, 1 << 22  # rows x cols at most: `run`, and `run(large_grids=True)` (csrc/forecast_launch.h)
 
@@ -102,8 +100,6 @@ class SharkForecast:
         ctx = self._context(filters_or_xy)
         L = ctx.L
         forecast = L.auvp_sf_forecast_large if large_grids else L.auvp_sf_forecast
-        forecast.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_double, _dp, C.c_int32, C.c_int32, _dp, C.c_int32,
-                             _dp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, _dp, _dp, _ip, _ip]
         rows, cols, n_cells = self.n_row, self.n_col, len(self.cell_bounds)
         if hasattr(filters_or_xy, "ctx"):
             F, N, xy = filters_or_xy.F, filters_or_xy.N, None
@@ -138,7 +134,7 @@ class SharkForecast:
         ctx._chk(forecast(ctx.h, _lib._p(box), rows, cols, float(self.cell_size), _lib._p(cells), n_cells, int(F),
                           _lib._p(xy) if xy is not None else None, int(N), _lib._p(pr), shared, int(which),
                           _lib._p(p_inf) if p_inf is not None else None, float(stay_prob), float(k), float(norm), R,
-                          _lib._p(grids) if grids is not None else None, _lib._p(prob), _lib._p(counts, _ip), _lib._p(status, _ip)))
+                          _lib._p(grids) if grids is not None else None, _lib._p(prob), _lib._p(counts), _lib._p(status)))
         self.last = Forecast(grids.reshape(F, R + 1, rows, cols) if grids is not None else None, prob.reshape(F, R + 1, n_cells),
                              counts.reshape(F, rows, cols), status, self.cell_bounds, ctx.last_kernel_ms(), ctx,
                              getattr(ctx, "sf_serial", 0) + 1, ctx.sf_last_kernel())

@@ -14,26 +14,15 @@ so the grids are bit-identical to the reference's.  `boundary` and the cells onl
 (:376-393) is outside the path: `cell_list` must be given, or `boundary` must be an axis-aligned
 rectangle (then `splitCell` below tiles it).
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
 
-_dp, _ip = _lib._dp, _lib._ip
 _ctx_cache = {}
-_bound = False
 
 
 def _bind():
-    global _bound
-    L = _lib.load()
-    if not _bound:
-        L.auvp_sog_convert.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, _ip,
-                                       _dp, C.c_int32, _ip, _ip, _ip, _dp, _dp]
-        L.auvp_sog_convert.restype = C.c_int
-        _bound = True
-    return L
+    return _lib.load()
 
 
 def _context(device):
@@ -75,21 +64,21 @@ def convert_arrays(ctx, cells, box, cell_size, bin_interval, detect_range, traj_
     L = _bind()
     cells = _lib._f64(cells, (-1, 4)) if len(cells) else np.zeros((0, 4))
     pts = _lib._f64(pts, (-1, 3)) if len(pts) else np.zeros((0, 3))
-    tl = np.ascontiguousarray(traj_len, dtype=np.int32)
+    tl = _lib._arr(traj_len, np.int32)
     if int(tl.sum()) != len(pts):
         raise ValueError("traj_len does not add up to the number of points")
     b = _lib._f64(np.asarray(box, dtype=np.float64), (4,))
     nb, rows, cols = (np.zeros(1, dtype=np.int32) for _ in range(3))
     args = (ctx.h, _lib._p(cells), len(cells), _lib._p(b), float(cell_size), float(bin_interval), float(detect_range),
-            len(tl), _lib._p(tl, _ip), _lib._p(pts))
-    rc = L.auvp_sog_convert(*args, 0, _lib._p(nb, _ip), _lib._p(rows, _ip), _lib._p(cols, _ip), None, None)
+            len(tl), _lib._p(tl), _lib._p(pts))
+    rc = L.auvp_sog_convert(*args, 0, _lib._p(nb), _lib._p(rows), _lib._p(cols), None, None)
     if rc != 0 and rc != -2:
         ctx._chk(rc)
     T = int(nb[0])
     bins = np.zeros((T, 2))
     grids = np.zeros((T, int(rows[0]), int(cols[0])))
     if T:
-        ctx._chk(L.auvp_sog_convert(*args, T, _lib._p(nb, _ip), _lib._p(rows, _ip), _lib._p(cols, _ip), _lib._p(bins),
+        ctx._chk(L.auvp_sog_convert(*args, T, _lib._p(nb), _lib._p(rows), _lib._p(cols), _lib._p(bins),
                                     _lib._p(grids)))
     return bins, grids
 

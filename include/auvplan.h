@@ -12,6 +12,7 @@
  */
 #ifndef AUVPLAN_H
 #define AUVPLAN_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

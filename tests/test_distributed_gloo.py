@@ -431,9 +431,10 @@ def test_rccl_unloadable_is_an_error_code_not_a_crash():
     import subprocess
     import sys
     code = (
-        "import ctypes as C, os, sys\n"
-        "L = C.CDLL(os.path.join(%r, 'auv_sim_amd', 'libauvplan.so'))\n"
-        "L.auvp_comm_library.restype = C.c_char_p\n"
+        "import ctypes as C, sys\n"
+        "sys.path.insert(0, %r)\n"
+        "from auv_sim_amd import _lib\n"
+        "L = _lib.load()\n"
         "assert L.auvp_comm_available() == 0\n"
         "assert L.auvp_comm_unique_id((C.c_uint8 * 128)()) == -6\n"
         "msg = L.auvp_comm_library().decode()\n"

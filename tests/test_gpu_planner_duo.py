@@ -2,7 +2,6 @@
 against prrt_kernel and the checker: bit-identical trees, bucket lists, counters, generator state / position and paths -- and
 the planning can be continued by generate_one_node steps of the other kernel.  (Rounds 3-4 also had a two / three-wavefront
 prrt_duo_kernel here; removed in round 5.)"""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -30,7 +29,6 @@ def _plan(ctx, w, starts, goals, seeds, max_step, duo, monkeypatch, **kw):
     monkeypatch.setenv("AUVP_PRRT_PIPE_DRAW", "1" if duo == 5 else "0")
     pb = PlannerBatch(ctx, starts, goals, w["rect"], max_step, seeds=seeds, **kw)
     s = pb.plan().copy()
-    ctx.L.auvp_prrt_last_kernel.restype = C.c_char_p
     assert ctx.L.auvp_prrt_last_kernel(ctx.h).decode() == {0: "prrt_kernel", 4: "prrt_pipe_kernel", 5: "prrt_pipe_kernel"}[duo]
     assert ctx.last_launch()[1] % {0: 64, 4: 256, 5: 320}[duo] == 0   # threads per workgroup: 4 / 5 wavefronts per episode
     assert ctx.pipeline_fallbacks()[0] == 0
@@ -103,7 +101,6 @@ def test_pipeline_continues_a_tree_with_and_without_the_link_mirror(ctx, next_ld
             g = [pb.grid(e) for e in range(n_ep)]
             pb.step(np.array([int(x[0][-1]) if len(x[0]) else 0 for x in g], dtype=np.int32))
         s = pb.plan().copy()
-        ctx.L.auvp_prrt_last_kernel.restype = C.c_char_p
         assert ctx.L.auvp_prrt_last_kernel(ctx.h).decode() == ("prrt_pipe_kernel" if pipe else "prrt_kernel")
         res.append((s, [pb.tree(e, s[e]) for e in range(n_ep)], pb.paths(s)))
     (a, ta, pa_), (b, tb, pb_) = res

@@ -10,7 +10,6 @@ ONE helper (csrc/planner_rrt_kernel.h prrt_bucket_of); here every planner kernel
   g2e_*     (the reference raises IndexError: in __init__, at the first random.choice of an empty occupied list, in the
             middle of planning())  ->  the episode's status is AUVP_ERR_ARG and its record stops where the reference stopped
 """
-import ctypes as C
 import glob
 import os
 import random
@@ -60,7 +59,6 @@ def _batch(ctx, g, kernel, E, seeds, step_log):
                           diff_max=float(g["diff_max"]), step_log=step_log and log_ok)
         # (a failing start is reported by the batch's first summaries; plan() then leaves such an episode alone)
         summ = pb.plan().copy()
-        ctx.L.auvp_prrt_last_kernel.restype = C.c_char_p
         assert ctx.L.auvp_prrt_last_kernel(ctx.h).decode() == kernel.split("/")[0]
         assert ctx.pipeline_fallbacks()[0] == 0
     finally:

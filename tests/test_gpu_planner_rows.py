@@ -30,7 +30,6 @@ def _plan(ctx, w, starts, goals, seeds, max_step, rows, monkeypatch, **kw):
     monkeypatch.setenv("AUVP_PRRT_LAT", "0")
     pb = PlannerBatch(ctx, starts, goals, w["rect"], max_step, seeds=seeds, **kw)
     s = pb.plan().copy()
-    ctx.L.auvp_prrt_last_kernel.restype = __import__("ctypes").c_char_p
     assert ctx.L.auvp_prrt_last_kernel(ctx.h).decode() == ("prrt_rows_kernel" if rows else "prrt_kernel")
     return pb, s
 
