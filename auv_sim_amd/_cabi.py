@@ -26,7 +26,7 @@ KFLAG_TIGHT_CULL, KFLAG_NN_EXACT = 1024, 2048  # auvp_rrt_launch_choice.kflags
 OPTION_NAMES = ("ROWS", "DUO", "TRIO", "QUAD", "TIGHT_CULL", "NN_EXACT", "LEAF_SWEEP_ALL", "NO_HABITAT_GRID", "RG_MAX_ENTRIES",
                 "NO_GRID_INDEX", "PRRT_LAT", "PRRT_PIPE", "PRRT_OBST_LDS", "PRRT_NEXT_LDS", "PRRT_ROWS", "ASTAR_NO_GRID",
                 "ASTAR_NO_LIST", "ASTAR_PAIR", "SOG_TILE", "PIPE_FALLBACK", "PRRT_PIPE_DRAW", "PRRT_BUCKET_LDS", "ROWS_STREAM", "ROWS_STREAM_CAP", "ROWS_STREAM_WAVES",
-                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR", "PRRT_ROWS_GRID", "SF_WIDE_MIN", "SF_WIDE_BLOCK")
+                "ROWS_WG_WAVES", "ROWS_STREAM_MIRROR", "PRRT_ROWS_GRID", "SF_WIDE_MIN", "SF_WIDE_BLOCK", "MEAS_TICKS")
 
 # ---- the type vocabulary of the table ----
 i, i32, i64, u64, f64, sz, s = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_size_t, C.c_char_p

@@ -17,6 +17,7 @@ from ._cabi import bp as _bp, dp as _dp, ip as _ip  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AUVPLAN_LIBRARY") or os.path.join(HERE, "libauvplan.so")  # override: kernel experiments
+MEAS_MAX_TICKS = 64  # option MEAS_TICKS, the k of replan_measure's shark_xy [k,F,2] (csrc/replan_ticks.h: REPLAN_MEAS_MAX_TICKS)
 
 # numpy element type -> pointer type (what _p picks for an array)
 _PTR = {np.dtype(t): C.POINTER(c) for t, c in (("f8", C.c_double), ("i4", C.c_int32), ("i8", C.c_int64), ("u8", C.c_uint64),
@@ -225,6 +226,7 @@ class Context:
         self.world_sizes = {}
         self.n_prob_sets = 0
         self.n_replan_auvs = 0
+        self._meas_steps = None  # k of the last replan_measure with shark_xy [k,F,2]; None: the [F,2] form
         self._world_stamp = 0  # counts set_world / set_habitats: a user that shares the context sees whether its world still stands
         self.session = None  # the open ReplanSession that owns this context's world, batch and fleet (rrt_dubins.py); None: none
 
@@ -573,7 +575,10 @@ class Context:
 
     def replan_measure(self, shark_of, n_per_shark, shark_xy):
         """auvp_replan_measure: the fleet's measurements [F, A, 5] of the sharks at shark_xy [F,2] from its committed states,
-        left in HBM.  Returns the table's device pointer (valid until the next call or replan_begin)."""
+        left in HBM.  Returns the table's device pointer (valid until the next call or replan_begin).
+        shark_xy [k,F,2], 1 <= k <= 64: k measurements per AUV along the bucket it committed last, [k, F, A, 5]
+        (replan_measure_ticks_kernel; csrc/replan_ticks.h, tracking.fleet_measurements_ticks) -- option MEAS_TICKS = k for this
+        call; it is back at what it was, set or unset, when the call returns or raises."""
         so = _arr(shark_of, np.int32, (-1,))
         if len(so) != self.n_replan_auvs:
             raise ValueError("shark_of has %d entries, the fleet %d AUVs" % (len(so), self.n_replan_auvs))
@@ -583,16 +588,37 @@ class Context:
         F = len(so) // A
         if so.min() < 0 or so.max() >= F or np.any(np.bincount(so, minlength=F) != A):
             raise ValueError("every shark 0 .. %d must be tracked by exactly %d AUVs" % (F - 1, A))
-        xy = _f64(shark_xy, (F, 2))
         ptr = C.c_void_p()
+        if np.ndim(shark_xy) == 3:
+            k = np.shape(shark_xy)[0]
+            if not 1 <= k <= MEAS_MAX_TICKS:
+                raise ValueError("shark_xy [k,F,2] needs 1 <= k <= %d, not %d" % (MEAS_MAX_TICKS, k))
+            if tuple(np.shape(shark_xy)[1:]) != (F, 2):
+                raise ValueError("shark_xy must be [k,%d,2], not %r" % (F, tuple(np.shape(shark_xy))))
+            xy = _f64(shark_xy, (k, F, 2))
+            before = self.get_option("MEAS_TICKS")
+            self.set_option("MEAS_TICKS", k)
+            try:
+                self._chk(self.L.auvp_replan_measure(self.h, _p(so), A, _p(xy), C.byref(ptr)))
+            finally:
+                self.set_option("MEAS_TICKS", before)
+            self._meas_steps = k
+            return ptr.value
+        xy = _f64(shark_xy, (F, 2))
+        k = self.get_option("MEAS_TICKS")  # (set by the caller: the library reads k x F positions)
+        if k is not None:
+            raise ValueError("option MEAS_TICKS = %d is set: pass shark_xy as [k,F,2]" % k)
         self._chk(self.L.auvp_replan_measure(self.h, _p(so), A, _p(xy), C.byref(ptr)))
+        self._meas_steps = None
         return ptr.value
 
     def replan_meas(self):
-        """the last replan_measure's table on the host, [F, A, 5] (auvp_replan_meas)"""
+        """the last replan_measure's table on the host (auvp_replan_meas): [F, A, 5], or [k, F, A, 5] where shark_xy was
+        [k,F,2]"""
         f, a = C.c_int32(0), C.c_int32(0)
         self._chk(self.L.auvp_replan_meas(self.h, C.byref(f), C.byref(a), None))
-        out = np.zeros((f.value, a.value, 5))
+        k = self._meas_steps
+        out = np.zeros((f.value, a.value, 5) if k is None else (k, f.value, a.value, 5))
         self._chk(self.L.auvp_replan_meas(self.h, None, None, _p(out)))
         return out
 

@@ -13,7 +13,7 @@
   X(NO_GRID_INDEX) X(PRRT_LAT) X(PRRT_PIPE) X(PRRT_OBST_LDS) X(PRRT_NEXT_LDS) X(PRRT_ROWS) X(ASTAR_NO_GRID)                 \
   X(ASTAR_NO_LIST) X(ASTAR_PAIR) X(SOG_TILE) X(PIPE_FALLBACK) X(PRRT_PIPE_DRAW) X(PRRT_BUCKET_LDS) X(ROWS_STREAM)           \
   X(ROWS_STREAM_CAP) X(ROWS_STREAM_WAVES) X(ROWS_WG_WAVES) X(ROWS_STREAM_MIRROR) X(PRRT_ROWS_GRID)          \
-  X(SF_WIDE_MIN) X(SF_WIDE_BLOCK)
+  X(SF_WIDE_MIN) X(SF_WIDE_BLOCK) X(MEAS_TICKS)
 enum AuvpOpt {
 #define AUVP_OPT_ENUM(n) OPT_##n,
   AUVP_OPTIONS(AUVP_OPT_ENUM)

@@ -15,8 +15,10 @@
 #include "replan_pick.h"
 #include "replan_apart.h"
 #include "replan_measure.h"
+#include "replan_ticks.h"
 
 extern "C" hipError_t auvpi_replan_measure_launch(const auvp::ReplanMeasureDev* M, hipStream_t stream);
+extern "C" hipError_t auvpi_replan_measure_ticks_launch(const auvp::ReplanMeasTicksDev* M, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_ticks_launch(const auvp::RrtBuffers* B, const auvp::ReplanTicksDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_pick_apart_launch(const auvp::ReplanPickDev* T, const auvp::ReplanApartDev* A, hipStream_t stream);
 extern "C" hipError_t auvpi_replan_words_launch(const auvp::RrtBuffers* B, const auvp::ReplanWordsDev* A, hipStream_t stream);
@@ -43,8 +45,9 @@ struct ReplanState {
   long long rows_committed = 0;            // rows of the log in use
   int rounds = 0;
   std::vector<long long> auv_rows;         // [n_auvs] rows committed per AUV
-  struct Piece { int32_t auv, n; int64_t src; };
+  typedef auvp::ReplanPiece Piece;         // (with the round that committed it: replan_ticks.h)
   std::vector<Piece> pieces;               // in round order
+  double last_span = 0.0;                  // round_span of the most recent auvp_replan_commit
   std::vector<auvp::ReplanRecord> rec_host;
   long long bytes_to_host = 0, bytes_traj = 0;
   double commit_ms = 0.0;                  // rrt_commit_kernel's time (with teams: and replan_team_kernel's; with auvp_replan_team_pick /
@@ -63,9 +66,11 @@ struct ReplanState {
   // commit copies as it copies the masks
   DevBuf tick_head, tick_xy, conflicts;
   bool pick_apart = false;
-  // auvp_replan_measure: the member table, the sharks' positions and the last table of measurements [meas_F][meas_A][5]
-  DevBuf meas_members, meas_shark, meas;
+  // auvp_replan_measure: the member table, the sharks' positions and the last table of measurements [meas_K][meas_F][meas_A][5];
+  // with option MEAS_TICKS the row groups' segments of the last commit too (replan_ticks.h)
+  DevBuf meas_members, meas_shark, meas, meas_seg;
   int meas_F = 0, meas_A = 0;              // 0: no measurement since auvp_replan_begin
+  int meas_K = 1;                          // steps of the last table: MEAS_TICKS in force at that measurement, 1 without it
 };
 
 ReplanState* replan_of(auvp_handle* h) {
@@ -168,6 +173,45 @@ int replan_launch(auvp_handle* h, ReplanState& S, const auvp::RrtBuffers* B, auv
   return AUVP_OK;
 }
 
+// auvp_replan_measure with option MEAS_TICKS = k set: k measurements along the segment every AUV committed in the most recent
+// auvp_replan_commit (replan_ticks.h), replan_measure_ticks_kernel.  shark_xy [k,F,2]; the table is [k,F,A,5].  A k outside
+// 1 .. 64 or a segment outside the log: nothing is launched and the last table stays.
+int replan_measure_ticks(auvp_handle* h, ReplanState& S, const auvp::ReplanMeasurePlan& plan, int32_t n_per_shark, const double* shark_xy,
+                         const void** meas_dev_out) {
+  const long long k = h->opt.opt_val[OPT_MEAS_TICKS];
+  const int n = (int)plan.members.size();
+  // (the bound is the log's reserved size: a piece lies where its winner's whole course was given room)
+  const auvp::ReplanTicksPlan tp = auvp::replan_ticks_plan(S.pieces.data(), S.pieces.size(), S.rounds - 1, S.n_auvs, plan.members.data(), n,
+                                                           S.log_rows, k);
+  if (tp.status == auvp::REPLAN_TICKS_BAD_K)
+    return fail(h, AUVP_ERR_ARG, "option MEAS_TICKS = %lld outside 1 .. %d", k, auvp::REPLAN_MEAS_MAX_TICKS);
+  if (tp.status != auvp::REPLAN_TICKS_OK) return fail(h, AUVP_ERR_STATE, "the last commit's segments do not fit the log (%d, %lld)", (int)tp.status, tp.bad);
+  HIPCHK(h, hipSetDevice(h->device));
+  S.meas_F = S.meas_A = 0;
+  int rc;
+  if ((rc = upload(h, S.meas_members, plan.members.data(), plan.members.size()))) return rc;
+  if ((rc = upload(h, S.meas_seg, tp.seg.data(), tp.seg.size()))) return rc;
+  if ((rc = upload(h, S.meas_shark, shark_xy, (size_t)k * (size_t)plan.F * 2))) return rc;
+  HIPCHK(h, S.meas.reserve((size_t)k * (size_t)n * auvp::REPLAN_MEAS_ROW * sizeof(double)));
+  auvp::ReplanMeasTicksDev M{};
+  M.n = n; M.A = n_per_shark; M.k = (int32_t)k;
+  M.members = S.meas_members.as<int32_t>(); M.seg = S.meas_seg.as<auvp::ReplanMeasSeg>();
+  M.last = S.last.as<double>(); M.log = S.log.as<double>(); M.shark_xy = S.meas_shark.as<double>();
+  M.meas = S.meas.as<double>();
+  M.round_span = S.last_span;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, auvpi_replan_measure_ticks_launch(&M, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (as auvp_replan_measure)
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms; h->last_grid = (n + auvp::REPLAN_MEAS_TICKS_WAVES - 1) / auvp::REPLAN_MEAS_TICKS_WAVES;
+  h->last_block = auvp::REPLAN_MEAS_TICKS_WAVES * 64; h->last_lds = 0;
+  S.meas_F = plan.F; S.meas_A = n_per_shark; S.meas_K = (int)k;
+  if (meas_dev_out) *meas_dev_out = S.meas.p;
+  return AUVP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -188,12 +232,14 @@ int auvp_replan_begin(auvp_handle* h, int32_t n_auvs, const double* start7, cons
   S.rounds = 0;
   S.auv_rows.assign((size_t)n_auvs, 0);
   S.pieces.clear();
+  S.last_span = 0.0;
   S.bytes_to_host = S.bytes_traj = 0;
   S.commit_ms = 0.0;
   S.n_teams = 0;  // (the teams were the old fleet's)
   S.max_team = 0;
   S.pick_pending = false;
   S.meas_F = S.meas_A = 0;
+  S.meas_K = 1;
   S.n_auvs = n_auvs;
   return AUVP_OK;
 }
@@ -210,6 +256,7 @@ int auvp_replan_measure(auvp_handle* h, const int32_t* shark_of, int32_t n_per_s
   if (plan.status == auvp::REPLAN_MEAS_BAD_SHARK)
     return fail(h, AUVP_ERR_ARG, "AUV %d: shark %d outside [0, %d)", plan.bad, shark_of[plan.bad], S.n_auvs / n_per_shark);
   if (plan.status != auvp::REPLAN_MEAS_OK) return fail(h, AUVP_ERR_ARG, "shark %d is not tracked by exactly %d AUVs", plan.bad, n_per_shark);
+  if (h->opt.opt_has[OPT_MEAS_TICKS]) return replan_measure_ticks(h, S, plan, n_per_shark, shark_xy, meas_dev_out);
   HIPCHK(h, hipSetDevice(h->device));
   S.meas_F = S.meas_A = 0;
   int rc;
@@ -227,7 +274,7 @@ int auvp_replan_measure(auvp_handle* h, const int32_t* shark_of, int32_t n_per_s
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->last_ms = ms; h->last_grid = (M.n + 63) / 64; h->last_block = 64; h->last_lds = 0;
-  S.meas_F = plan.F; S.meas_A = n_per_shark;
+  S.meas_F = plan.F; S.meas_A = n_per_shark; S.meas_K = 1;
   if (meas_dev_out) *meas_dev_out = S.meas.p;
   return AUVP_OK;
 }
@@ -241,7 +288,7 @@ int auvp_replan_meas(auvp_handle* h, int32_t* n_sharks, int32_t* n_per_shark, do
   if (n_per_shark) *n_per_shark = S.meas_A;
   if (!meas) return AUVP_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t bytes = (size_t)S.meas_F * (size_t)S.meas_A * auvp::REPLAN_MEAS_ROW * sizeof(double);
+  const size_t bytes = (size_t)S.meas_K * (size_t)S.meas_F * (size_t)S.meas_A * auvp::REPLAN_MEAS_ROW * sizeof(double);
   HIPCHK(h, hipMemcpyAsync(meas, S.meas.p, bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   S.bytes_to_host += (long long)bytes;
@@ -337,12 +384,13 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of, 
   for (int g = 0; g < G; g++) {
     const auvp::ReplanRecord& r = S.rec_host[(size_t)g];
     const int n = r.n_committed > 0 && r.n_committed <= slots[(size_t)g].path_len ? r.n_committed : 0;
-    if (n) S.pieces.push_back(ReplanState::Piece{slots[(size_t)g].auv, n, slots[(size_t)g].log_off});
+    if (n) S.pieces.push_back(ReplanState::Piece{slots[(size_t)g].auv, n, slots[(size_t)g].log_off, S.rounds, 0});
     S.auv_rows[(size_t)slots[(size_t)g].auv] += n;
     S.rows_committed += n;
   }
   S.log_rows += total;
   S.rounds++;
+  S.last_span = round_span;
   S.commit_ms += ms;
   h->last_ms = ms; h->last_grid = G; h->last_block = 64; h->last_lds = 0;
   if (out) memcpy(out, S.rec_host.data(), (size_t)G * sizeof(auvp::ReplanRecord));

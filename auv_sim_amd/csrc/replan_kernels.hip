@@ -10,6 +10,7 @@
 //   rrt_course_words_kernel, replan_team_pick_kernel  the team-aware winner selection (replan_pick.h), see below
 //   rrt_course_ticks_kernel, replan_team_pick_apart_kernel  the selection that keeps teammates' courses apart (replan_apart.h)
 //   replan_measure_kernel  the fleet's range / bearing measurements of its sharks from the committed states (replan_measure.h)
+//   replan_measure_ticks_kernel  k such measurements per AUV along the bucket it committed last (replan_ticks.h)
 //
 // Entry points for the host side (replan_host.h): internal, hidden visibility, not part of the C-ABI.
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "replan_apart.h"
 #include "rrt_course_walk.h"
 #include "replan_measure.h"
+#include "replan_ticks.h"
 #include "auvp_math_late.h"
 
 namespace auvp {
@@ -474,7 +476,60 @@ static __global__ __launch_bounds__(REPLAN_MEAS_THREADS) void replan_measure_ker
   o[4] = replan_atan2_round(dy, dx, auvp_atan2_late(dy, dx)) - theta;
 }
 
+// ---- k measurements along the last committed bucket (replan_ticks.h) --------------------------------------------------------------
+//
+// One wavefront per row group (f, a) of meas [k][F][A][5], that is per AUV; REPLAN_MEAS_TICKS_WAVES of them per workgroup, which
+// share nothing (no LDS, no barrier).  seg, members and k come from the host (replan_ticks_plan: every row inside the log, every
+// AUV inside the fleet, 1 <= k <= 64).
+//   row search   lane j holds tau_j.  The lanes take the segment's row times 64 at a time, one row each; for every tick a vote
+//                over the chunk (t_i <= tau_j) is the wave-wide reduction: the greatest qualifying index of the chunk is the
+//                vote's top bit, and lane j keeps it.  The chunks ascend, so a later one overrides: the greatest index of the
+//                whole segment, with no assumption on the order of the times.  n / 64 loads per lane and k votes per chunk --
+//                a per-tick max over strided lane-local candidates would read every time k times for the same answer.
+//   row compute  lanes 0 .. k-1, one tick each: replan_measure_kernel's five doubles from the chosen row (the AUV's state where
+//                the segment is empty) -- the bearing's double-double correction on up to 64 lanes at once.
+//   stores       plain vector stores, step-major: row (j, f, a) at ((j * F + f) * A + a) * 5.
+static __global__ __launch_bounds__(REPLAN_MEAS_TICKS_WAVES * 64) void replan_measure_ticks_kernel(ReplanMeasTicksDev M) {
+  const int i = (int)blockIdx.x * REPLAN_MEAS_TICKS_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= M.n) return;  // (the whole wavefront)
+  const int lane = lane_id();
+  const int k = M.k;
+  const ReplanMeasSeg sg = M.seg[i];
+  const double* seg = M.log + (size_t)REPLAN_ROW * (size_t)sg.off;
+  int best = 0;
+  if (sg.n > 0) {  // (the same on every lane)
+    const double tau = replan_meas_tick_time(seg[4], M.round_span, k, lane < k ? lane : k - 1);
+    for (int c = 0; c < sg.n; c += 64) {
+      const int r = c + lane;
+      const bool valid = r < sg.n;
+      const double t = valid ? seg[(size_t)REPLAN_ROW * (size_t)r + 4] : 0.0;
+      for (int j = 0; j < k; j++) {
+        const double tau_j = __shfl(tau, j);  // (by every lane: outside the vote's condition)
+        const unsigned long long mask = wave_ballot(valid && replan_meas_tick_reached(t, tau_j));
+        if (mask != 0 && lane == j) best = c + 63 - __clzll((long long)mask);
+      }
+    }
+  }
+  if (lane >= k) return;
+  const double* src = sg.n > 0 ? seg + (size_t)REPLAN_ROW * (size_t)best : M.last + (size_t)REPLAN_ROW * (size_t)M.members[i];
+  const int f = i / M.A, F = M.n / M.A;
+  const double* shark = M.shark_xy + 2 * ((size_t)lane * (size_t)F + (size_t)f);
+  const double x = src[0], y = src[1], theta = src[2];
+  const double dx = shark[0] - x, dy = shark[1] - y;
+  double* o = M.meas + (size_t)REPLAN_MEAS_ROW * ((size_t)lane * (size_t)M.n + (size_t)i);
+  o[0] = x; o[1] = y; o[2] = theta;
+  o[3] = auvp_sqrt_plain(dx * dx + dy * dy);
+  o[4] = replan_atan2_round(dy, dx, auvp_atan2_late(dy, dx)) - theta;
+}
+
 }  // namespace auvp
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_measure_ticks_launch(const auvp::ReplanMeasTicksDev* M, hipStream_t stream) {
+  if (M->n <= 0 || M->A <= 0 || !auvp::replan_meas_ticks_ok(M->k)) return hipSuccess;
+  const int blocks = (M->n + auvp::REPLAN_MEAS_TICKS_WAVES - 1) / auvp::REPLAN_MEAS_TICKS_WAVES;
+  hipLaunchKernelGGL(auvp::replan_measure_ticks_kernel, dim3(blocks), dim3(auvp::REPLAN_MEAS_TICKS_WAVES * 64), 0, stream, *M);
+  return hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t auvpi_replan_measure_launch(const auvp::ReplanMeasureDev* M, hipStream_t stream) {
   if (M->n <= 0) return hipSuccess;

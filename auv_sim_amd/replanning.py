@@ -500,6 +500,10 @@ class DeviceRounds(_Rounds):
         row_off, rows_all = self.s.rrt._ctx.replan_traj()
         return {e: rows_all[row_off[e]:row_off[e + 1]] for e in done}
 
+    def tails(self, n):
+        row_off, rows_all = self.s.rrt._ctx.replan_traj()
+        return [rows_all[row_off[e + 1] - n[e]:row_off[e + 1]].copy() for e in range(len(n))]
+
 
 class HostRounds(_Rounds):
     """commit="host": the winners' courses come to the host -- every candidate's with team_pick or team_separation, where the
@@ -578,6 +582,9 @@ class HostRounds(_Rounds):
     def rows(self, done):
         return {e: np.concatenate(self.committed[e] + [np.zeros((0, 7))]) for e in done}
 
+    def tails(self, n):
+        return [self.committed[e][-1].copy() if n[e] else np.zeros((0, 7)) for e in range(len(n))]
+
 
 class ReplanSession:
     """RRT.replanning_batch as a resumable object (RRT.replanning_session gives the commit="device" one).  The host keeps [N]
@@ -634,6 +641,17 @@ class ReplanSession:
     def active(self):
         """indices of the AUVs that would plan in the next round"""
         return np.flatnonzero(self._alive & (self._last[:, 4] + self.round_span < self._horizon_end))
+
+    def last_segments(self):
+        """[N] arrays [n,7]: the rows every AUV committed in the most recent round, row 0 the state it had before it -- empty for
+        an AUV that did not plan in that round or found no winner, and for everybody before the first round.  With
+        commit="device" this downloads the trajectories (replan_traj): for checks, not for a loop that is to stay on the device."""
+        self._open("last_segments")
+        n = np.zeros(len(self._starts), dtype=np.int64)
+        if self._log:
+            n[self._log[-1][0]] = self._log[-1][1]["n_committed"]
+        with self._Own(self):
+            return self._back.tails(n)
 
     def _open(self, what):
         if self.closed:

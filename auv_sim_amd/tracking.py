@@ -142,6 +142,72 @@ def fleet_measurements(last7, shark_of, shark_xy):
     return meas
 
 
+MEAS_MAX_TICKS = 64  # filter steps (ticks) per round: csrc/replan_ticks.h, REPLAN_MEAS_MAX_TICKS
+
+
+def tick_times(lo, round_span, k):
+    """the k tick times of the bucket that starts at lo: lo + (j + 1) * (round_span / k) for j < k - 1, and lo + 1.0 * round_span
+    -- the bucket's hi (first_bucket_commit) -- for the last, however k * (round_span / k) rounds.  Every operation rounded on
+    its own, as csrc/replan_ticks.h has them."""
+    lo, span = float(lo), float(round_span)
+    step = span / float(k)
+    return [lo + float(j + 1) * step for j in range(k - 1)] + [lo + 1.0 * span]
+
+
+def tick_row(times, tau):
+    """the greatest index i with times[i] <= tau (a NaN never qualifies), 0 where there is none: where an AUV that committed
+    rows at `times` is when the clock shows tau -- at the last point it reached, nothing interpolated (replanning.course_ticks).
+    A linear scan: the times need not ascend."""
+    best = 0
+    for i, t in enumerate(times):
+        if float(t) <= tau:
+            best = i
+    return best
+
+
+def fleet_measurements_ticks(segments, last7, shark_of, shark_xy_k, round_span):
+    """k measurements per AUV along the bucket it committed last -- the definition replan_measure_ticks_kernel is held to
+    (csrc/replan_ticks.h).  segments[i]: the [n,7] rows AUV i committed in the most recent round, row 0 the state it had before
+    (so its time is the bucket's lo), or an empty array: every tick from last7[i] (an AUV that stopped planning or found no
+    winner, a fleet before its first round).  last7 [N,7], shark_of [N], shark_xy_k [k,F,2] the sharks' true positions at the
+    ticks, 1 <= k <= 64; round_span: of that round (read only where a segment has rows).  Tick j of AUV i: the row
+    tick_row(segments[i][:, 4], tick_times(segments[i][0, 4], round_span, k)[j]).  Returns meas [k, F, A, 5], row (j, f, a) as
+    fleet_measurements writes it from that row's x, y, theta against shark_xy_k[j, f].  With k = 1 and no segments it is
+    fleet_measurements.  ValueError for a bad k, bad shapes, and unless every shark is tracked by the same number of AUVs."""
+    last = np.asarray(last7, dtype=np.float64)
+    xy = np.asarray(shark_xy_k, dtype=np.float64)
+    if last.ndim != 2 or last.shape[1] != 7:
+        raise ValueError("last7 must be [N,7]")
+    if xy.ndim != 3 or xy.shape[2] != 2:
+        raise ValueError("shark_xy_k must be [k,F,2]")
+    k = xy.shape[0]
+    if not 1 <= k <= MEAS_MAX_TICKS:
+        raise ValueError("need 1 <= k <= %d ticks, not %d" % (MEAS_MAX_TICKS, k))
+    N = len(last)
+    if len(list(shark_of)) != N or len(segments) != N:
+        raise ValueError("shark_of has %d entries, segments %d, last7 %d rows" % (len(list(shark_of)), len(segments), N))
+    mem = shark_members(shark_of, xy.shape[1])
+    F, A = mem.shape
+    segs = []
+    for i, s in enumerate(segments):
+        s = np.zeros((0, 7)) if s is None else np.asarray(s, dtype=np.float64)
+        if s.size and (s.ndim != 2 or s.shape[1] != 7):
+            raise ValueError("segments[%d] must be [n,7]" % i)
+        segs.append(s.reshape(-1, 7))
+    meas = np.zeros((k, F, A, 5))
+    for f in range(F):
+        for a in range(A):
+            i = int(mem[f, a])
+            seg = segs[i]
+            taus = tick_times(seg[0, 4], round_span, k) if len(seg) else None
+            for j in range(k):
+                row = seg[tick_row(seg[:, 4], taus[j])] if len(seg) else last[i]
+                x, y, theta = (float(v) for v in row[:3])
+                dx, dy = float(xy[j, f, 0]) - x, float(xy[j, f, 1]) - y
+                meas[j, f, a] = (x, y, theta, math.sqrt(dx * dx + dy * dy), math.atan2(dy, dx) - theta)
+    return meas
+
+
 def first_bin_of_time(bins, t):
     """index of the first bin [t0, t1] of bins [T,2] with t0 <= t <= t1; T - 1 where there is none (past the end)"""
     b = np.asarray(bins, dtype=np.float64).reshape(-1, 2)
@@ -169,17 +235,30 @@ class FleetTracker:
       3. session.set_shark_grids(fc, first_bin=b_r), b_r the first world bin that contains r * round_span (the last bin past
          the end): the forecast speaks from now on;
       4. session.round().
-    Limits: every shark is tracked by the same number of AUVs (ValueError); one filter step per round; b_r comes from the
-    NOMINAL time r * round_span, not from the AUVs' own clocks (their committed times drift apart by less than a round).
+    filter_steps = k > 1: the filters hear the sharks k times per round, from where the AUVs were at k ticks of the bucket they
+    just travelled (fleet_measurements_ticks; csrc/replan_ticks.h).  Round r consumes tracks[:, r*k : (r+1)*k] -- sample r*k + j
+    is the shark at tick j, the round's last sample is "now" -- and the loop ends when fewer than k samples remain.  Step 1
+    becomes meas [k, F, A, 5]: measure="device" is one replan_measure call (replan_measure_ticks_kernel) and one
+    run_dev_meas(..., n_steps=k), k * F * 2 doubles in and nothing else across the bus; measure="host" downloads the
+    trajectories (ReplanSession.last_segments) for fleet_measurements_ticks.  In round 0 nothing is committed yet: all k
+    measurements are taken from the start states.  step() then returns estimates_all [k,F,2] beside estimates, the last step's.
+    Limits: every shark is tracked by the same number of AUVs (ValueError); at most 64 filter steps per round, the sharks
+    sampled at equal ticks of it; b_r comes from the NOMINAL time r * round_span, not from the AUVs' own clocks (their
+    committed times drift apart by less than a round).
     tracks [F, S, 2]; shark_of [N]; the remaining keyword arguments are RRT.replanning_session's (shark_of is passed on)."""
 
     def __init__(self, rrt, forecast, filters, tracks, shark_of, prior, forecast_rounds, method=("ave", 1), measure="device",
-                 large_grids=False, **session_args):
+                 large_grids=False, filter_steps=1, **session_args):
         if measure not in ("device", "host"):
             raise ValueError("measure must be 'device' or 'host', not %r" % (measure,))
         self.tracks = np.asarray(tracks, dtype=np.float64)
         if self.tracks.ndim != 3 or self.tracks.shape[2] != 2:
             raise ValueError("tracks must be [F, S, 2]")
+        if isinstance(filter_steps, (bool, np.bool_)) or int(filter_steps) != filter_steps or not 1 <= int(filter_steps) <= MEAS_MAX_TICKS:
+            raise ValueError("filter_steps must be an integer in 1 .. %d, not %r" % (MEAS_MAX_TICKS, filter_steps))
+        self.filter_steps = int(filter_steps)
+        if self.tracks.shape[1] < self.filter_steps:
+            raise ValueError("tracks has %d samples, fewer than filter_steps = %d" % (self.tracks.shape[1], self.filter_steps))
         F = self.tracks.shape[0]
         if F != filters.F:
             raise ValueError("tracks has %d sharks, the filter batch %d" % (F, filters.F))
@@ -198,22 +277,35 @@ class FleetTracker:
 
     def step(self):
         """one round of the loop; the round's dict (ReplanSession.round) plus estimates [F,2], the filters' means after the
-        update -- or None once no AUV plans any more or the tracks have ended"""
+        update (with filter_steps = k > 1: after the round's last step, and estimates_all [k,F,2], after each) -- or None once no
+        AUV plans any more or the tracks have ended"""
         s = self.session
-        r = s.round_index
-        if r >= self.tracks.shape[1] or len(s.active()) == 0:
+        r, k = s.round_index, self.filter_steps
+        if (r + 1) * k > self.tracks.shape[1] or len(s.active()) == 0:
             return None
-        shark = self.tracks[:, r, :]
-        if self.measure == "device":
-            ptr = self.rrt._ctx.replan_measure(self.shark_of, self.A, shark)
-            self.filters.run_dev_meas(ptr, self.A, shark[None])
+        if k == 1:
+            shark = self.tracks[:, r, :]
+            if self.measure == "device":
+                ptr = self.rrt._ctx.replan_measure(self.shark_of, self.A, shark)
+                self.filters.run_dev_meas(ptr, self.A, shark[None])
+            else:
+                self.filters.run(meas=fleet_measurements(s.last, self.shark_of, shark), shark_xy=shark[None])
         else:
-            self.filters.run(meas=fleet_measurements(s.last, self.shark_of, shark), shark_xy=shark[None])
+            shark = np.ascontiguousarray(self.tracks[:, r * k:(r + 1) * k, :].transpose(1, 0, 2))  # [k,F,2]
+            if self.measure == "device":
+                ptr = self.rrt._ctx.replan_measure(self.shark_of, self.A, shark)
+                self.filters.run_dev_meas(ptr, self.A, shark, n_steps=k)
+            else:
+                meas = fleet_measurements_ticks(s.last_segments(), s.last, self.shark_of, shark, s.round_span)
+                self.filters.run(meas=meas, shark_xy=shark)
         fc = self._forecast()
         s.set_shark_grids(fc, first_bin=first_bin_of_time(self.rrt._bins, r * s.round_span))
         out = s.round()
         if out is not None:
-            out["estimates"] = self.filters.estimates()[0][0]
+            est = self.filters.estimates()[0]
+            out["estimates"] = est[-1]
+            if k > 1:
+                out["estimates_all"] = est
         return out
 
     def run(self, as_arrays=False):

@@ -274,11 +274,21 @@ int auvp_replan_commit(auvp_handle* h, int32_t n_active, const int32_t* auv_of /
  * to the nearest double -- csrc/replan_measure.h: what math.sqrt and math.atan2 give).  An AUV that no longer plans keeps measuring
  * from its last committed state.  *meas_dev_out (may be NULL) gets the table's device pointer: valid until the next
  * auvp_replan_measure or auvp_replan_begin on this handle; the call synchronises its stream before it returns, so a copy enqueued
- * afterwards on another handle's stream on the same device is ordered behind it.  AUVP_ERR_STATE without auvp_replan_begin. */
+ * afterwards on another handle's stream on the same device is ordered behind it.  AUVP_ERR_STATE without auvp_replan_begin.
+ * With option MEAS_TICKS = k set (1 <= k <= 64; otherwise AUVP_ERR_ARG, nothing is launched and the last table stays): k
+ * measurements per AUV along the segment it committed in the most recent auvp_replan_commit (csrc/replan_ticks.h;
+ * replan_measure_ticks_kernel, one wavefront per AUV).  shark_xy is then [k,F,2], the sharks at the k ticks, and the table
+ * [k, F, n_per_shark, 5], step-major: auvp_pf_run's meas for k steps.  Tick j < k - 1 is at lo + (j + 1) * (round_span / k), the
+ * last at lo + 1.0 * round_span, with lo the time of the segment's first row (the state before that commit) and round_span that
+ * commit's; the AUV is at the segment row with the greatest index whose time is <= the tick (row 0 if none; nothing is
+ * interpolated), so the last tick is the committed state.  An AUV without a segment in that commit -- it no longer plans, its
+ * group had no winner, or nothing has been committed yet -- measures from its state at every tick.  k = 1 gives the table of
+ * the call without the option, bit for bit. */
 int auvp_replan_measure(auvp_handle* h, const int32_t* shark_of /* [n_auvs] */, int32_t n_per_shark, const double* shark_xy /* [F,2] */,
                         const void** meas_dev_out);
 /* The last auvp_replan_measure's table copied to the host (for checks): n_sharks, n_per_shark, meas [F, n_per_shark, 5]; each may
- * be NULL.  AUVP_ERR_STATE without one since auvp_replan_begin. */
+ * be NULL.  After a measurement under option MEAS_TICKS = k the whole table, k * F * n_per_shark * 5 doubles ([k, F, n_per_shark,
+ * 5]), with the k in force at that measurement.  AUVP_ERR_STATE without one since auvp_replan_begin. */
 int auvp_replan_meas(auvp_handle* h, int32_t* n_sharks, int32_t* n_per_shark, double* meas);
 /* The team-aware winner selection ("claims", csrc/replan_pick.h), in place of auvp_rrt_group_best in a round: the batch that
  * just ran holds K trees for each of n_active AUVs, group g = episodes g*K .. g*K+K-1 = AUV auv_of[g].  Every group first gets
